@@ -70,3 +70,27 @@ def test_rendezvous_port_is_below_the_ephemeral_range():
         assert 20000 <= p < 32768
         with socket.socket() as s:
             s.bind(("127.0.0.1", p))
+
+
+def test_dumped_output_is_the_frame_or_the_same_seeded_sample(bench):
+    """--dump-outputs: float32, the whole result plane while it fits, else the same DUMP_PIXELS pixels (seeded, raster order) in every run."""
+    small = torch.arange(48 * 64 * 4, dtype=torch.float32).reshape(48, 64, 4).to(torch.float16)
+    got = bench.output_sample(small)
+    assert got.dtype == np.float32 and got.shape == (48, 64, 4) and np.array_equal(got, small.float().numpy())
+    H, W = 1024, 2304                      # more pixels than DUMP_PIXELS
+    big = torch.arange(H * W, dtype=torch.float64).repeat_interleave(4).reshape(H, W, 4).float()
+    a, b = bench.output_sample(big), bench.output_sample(big.clone())
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_PIXELS, 4) and a.nbytes <= 64 << 20 and np.array_equal(a, b)
+    idx = a[:, 0].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and idx[-1] < H * W and (a == idx[:, None]).all()
+
+
+def test_dump_outputs_is_refused_where_there_is_no_single_frame(bench, monkeypatch, capsys):
+    for argv in (["--gpus", "2"], ["--strips"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv, "--dump-outputs", "out"])
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        assert e.value.code == 2 and "--dump-outputs" in capsys.readouterr().err
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.dump_outputs == "out" and not args.full

@@ -514,13 +514,13 @@ def test_bench_ends_loudly_when_the_communicator_cannot_come_up():
 
 
 def test_bench_strips_line_on_one_gpu(G):
-    """`bench.py --gpus 1 --strips`: the N > 1 code path (C++ strip driver, world size 1) prints every field of the N > 1 line."""
+    """`bench.py --gpus 1 --strips --full`: the N > 1 code path (C++ strip driver, world size 1) prints every field of the N > 1 line."""
     import subprocess
     import sys
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):      # an in-process group of this pytest run may own that port
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strips", "--steps", "3", "--warmup", "1", "--workload", "4k", "--prime-ms", "0", "--prime-frames", "0"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strips", "--full", "--steps", "3", "--warmup", "1", "--workload", "4k", "--prime-ms", "0", "--prime-frames", "0"],
                        env=env, capture_output=True, text=True, timeout=500)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
@@ -537,7 +537,7 @@ def test_bench_strips_leg_that_never_returns_leaves_the_measured_legs(G):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strips", "--steps", "3", "--warmup", "1", "--workload", "1080p", "--prime-ms", "0", "--prime-frames", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--strips", "--full", "--steps", "3", "--warmup", "1", "--workload", "1080p", "--prime-ms", "0", "--prime-frames", "0",
            "--leg-timeout", "15"]
     p = subprocess.run(cmd, env=dict(env, SVGF_BENCH_HANG_AT="plan ghost"), capture_output=True, text=True, timeout=500)
     assert p.returncode == 5, (p.returncode, p.stderr[-2000:])
@@ -548,6 +548,29 @@ def test_bench_strips_leg_that_never_returns_leaves_the_measured_legs(G):
     p = subprocess.run(cmd, env=dict(env, SVGF_BENCH_HANG_AT="headline"), capture_output=True, text=True, timeout=500)
     assert p.returncode == 4 and not [ln for ln in p.stdout.splitlines() if ln.startswith("{")], (p.returncode, p.stdout[-500:], p.stderr[-1500:])
     assert "did not finish" in p.stderr
+
+
+def test_bench_plain_run_and_its_dumped_output(G, tmp_path):
+    """`bench.py --dump-outputs DIR`: the result of the last timed frame, the same bits in every run with the same arguments — a plain run twice, and a
+    --full run whose further windows and legs come after it.  The plain line holds the headline alone; --full adds the spread and the other legs."""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--workload", "1080p", "--prime-ms", "0", "--prime-frames", "60"]
+    lines, outs = [], []
+    for k, extra in enumerate(([], [], ["--full", "--no-cpu", "--windows", "3"])):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / str(k))], env=env, capture_output=True, text=True, timeout=500)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]))
+        outs.append(np.load(tmp_path / str(k) / "output.npy"))
+    for d in lines:
+        assert d["steps"] == 6 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(1920 * 1080 / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-3) and d["roofline"]["frac"] > 0
+    assert not {"also", "pan", "cpu_baseline", "windows_ms", "cold_frames_ms"} & set(lines[0])
+    assert "pan" in lines[2] and "cpu_baseline" not in lines[2] and len(lines[2]["windows_ms"]) == 3 and lines[2]["windows_ms"][0] == pytest.approx(lines[2]["ms_per_step"], abs=1e-4)
+    assert outs[0].dtype == np.float32 and outs[0].shape == (1080, 1920, 4) and np.isfinite(outs[0]).all() and outs[0][..., :3].max() > 0
+    assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
 
 
 @pytest.mark.parametrize("storage", ["f32", "f16"])

@@ -15,13 +15,13 @@ python3 tools/make_traffic.py gpurun_out/prof_${TAG}_4k_f32 3840x2160_f32 $RN > 
 python3 tools/make_traffic.py gpurun_out/prof_${TAG}_4k_f16 3840x2160_f16 $RN > /dev/null
 python3 tools/make_traffic.py gpurun_out/prof_${TAG}_1080p 1920x1080_f32 $RN > /dev/null
 cp profiles/hbm_traffic.json $O/hbm_traffic.json
-python3 bench.py 2>$O/bench_4k_f32.err | grep "^{" > $O/bench_4k_f32.json
-python3 bench.py --storage f16 --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_4k_f16.json
-python3 bench.py --workload 1080p --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_1080p_f32.json
-python3 bench.py --workload 8k --no-cpu --no-extra --steps 20 2>/dev/null | grep "^{" > $O/bench_8k_f32.json
-python3 bench.py --fuse --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_4k_f32_pair_launch.json
-python3 bench.py --frames-in-flight 2 --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_4k_f32_two_in_flight.json
-python3 bench.py --strips --workload 8k --steps 20 --warmup 3 2>/dev/null | grep "^{" > $O/bench_8k_f32_stripdriver_1gpu.json
+python3 bench.py --full 2>$O/bench_4k_f32.err | grep "^{" > $O/bench_4k_f32.json
+python3 bench.py --full --storage f16 --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_4k_f16.json
+python3 bench.py --full --workload 1080p --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_1080p_f32.json
+python3 bench.py --full --workload 8k --no-cpu --no-extra --steps 20 2>/dev/null | grep "^{" > $O/bench_8k_f32.json
+python3 bench.py --full --fuse --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_4k_f32_pair_launch.json
+python3 bench.py --full --frames-in-flight 2 --no-cpu --no-extra 2>/dev/null | grep "^{" > $O/bench_4k_f32_two_in_flight.json
+python3 bench.py --full --strips --workload 8k --steps 20 --warmup 3 2>/dev/null | grep "^{" > $O/bench_8k_f32_stripdriver_1gpu.json
 python3 tools/strip_sim.py --rounds 3 2>&1 | grep -E "ms/frame|whole|wire|MB per" > $O/strip_sim.txt
 python3 tools/cold_frames.py 2>&1 | grep "frame" > $O/cold_frames.txt
 # the seeded sweep of the parity / bit-identity claims, LAST (whatever it finds, the measurements above stand): ${FUZZ_MINUTES:-10} minutes

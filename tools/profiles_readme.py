@@ -52,11 +52,11 @@ def main(tag):
     rows, notes = [], []
     b = load(f"{tag}_bench_4k_f32.json")
     files = [
-        (f"{tag}_bench_4k_f32.json", "`bench.py` (defaults: 3840x2160 fp32, 5 windows of 50 frames, pan / 1080p / fp16 / general-path extras, cpu_baseline) at the round's final sources"),
-        (f"{tag}_bench_4k_f16.json, {tag}_bench_1080p_f32.json, {tag}_bench_8k_f32.json", "`bench.py --storage f16 | --workload 1080p | --workload 8k` (`--no-cpu --no-extra`)"),
-        (f"{tag}_bench_4k_f32_pair_launch.json", "`bench.py --fuse`: iterations 0 + 1 as one launch (`svgf_atrous_pair`), same call"),
-        (f"{tag}_bench_4k_f32_two_in_flight.json", "`bench.py --frames-in-flight 2`: `svgf_set_frames_in_flight(2)` — iterations 1-4 of a frame beside the next frame's temporal launch (stage times are brackets of overlapping launches)"),
-        (f"{tag}_bench_8k_f32_stripdriver_1gpu.json", "`bench.py --gpus 1 --strips --workload 8k`: the N > 1 code path (C++ strip driver, every halo plan, the pan, the one-GPU reference) on ONE GPU"),
+        (f"{tag}_bench_4k_f32.json", "`bench.py --full` (3840x2160 fp32, 5 windows of 50 frames, pan / 1080p / fp16 / general-path extras, cpu_baseline) at the round's final sources"),
+        (f"{tag}_bench_4k_f16.json, {tag}_bench_1080p_f32.json, {tag}_bench_8k_f32.json", "`bench.py --full --storage f16 | --workload 1080p | --workload 8k` (`--no-cpu --no-extra`)"),
+        (f"{tag}_bench_4k_f32_pair_launch.json", "`bench.py --full --fuse`: iterations 0 + 1 as one launch (`svgf_atrous_pair`), same call"),
+        (f"{tag}_bench_4k_f32_two_in_flight.json", "`bench.py --full --frames-in-flight 2`: `svgf_set_frames_in_flight(2)` — iterations 1-4 of a frame beside the next frame's temporal launch (stage times are brackets of overlapping launches)"),
+        (f"{tag}_bench_8k_f32_stripdriver_1gpu.json", "`bench.py --gpus 1 --strips --full --workload 8k`: the N > 1 code path (C++ strip driver, every halo plan, the pan, the one-GPU reference) on ONE GPU"),
         (f"{tag}_rocprofv3_summary_4k_f32.txt, _4k_f16.txt, _1080p_f32.txt", "`tools/prof.sh`: kernel stats (`rocprofv3 --kernel-trace --stats`) + SQ / LDS / FETCH_SIZE / WRITE_SIZE counters (separate `--pmc` passes) of `bench.py --steps 20 --warmup 3 --no-cpu --no-extra [...]`"),
         (f"{tag}_kernel_stats_4k_f32.csv", f"the raw `*_kernel_stats.csv` of the SAME trace run `{tag}_rocprofv3_summary_4k_f32.txt` was condensed from"),
         (f"{tag}_bench_under_rocprofv3_4k_f32.json", "the bench line that traced run printed itself (the library's HIP events under the tracer)"),
