@@ -76,10 +76,10 @@ int check_gbuf(svgf_ctx* c, const svgf_gbuffer* g, bool need_uv, const char* wha
     return SVGF_OK;
 }
 
-hipEvent_t take_event(svgf_ctx* c) {
-    if (!c->pool.empty()) { hipEvent_t e = c->pool.back(); c->pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
+Event take_event(svgf_ctx* c) {
+    Event e;
+    if (c->pool.empty()) (void)acquire(e, hipEventCreate);
+    else { e = std::move(c->pool.back()); c->pool.pop_back(); }
     return e;
 }
 
@@ -102,33 +102,30 @@ int alloc_flags(svgf_ctx* c) {
     unsigned long long cap = 0;
     if (int rc = capture_of(c, &cap); rc != SVGF_OK) return rc;
     if (cap) return fail(c, SVGF_ERR_INVALID, "the context's stream is being captured and this call's first use of the context allocates its scratch: enqueue one call before the capture begins");
-    // all or none: a failed allocation leaves nothing behind that a later call would mistake for a complete set
-    auto drop = [&]() {
-        if (c->young_masks) (void)hipFree(c->young_masks);
-        if (c->young_list) (void)hipFree(c->young_list);
-        if (c->young_count) (void)hipFree(c->young_count);
-        if (c->nan_count) (void)hipFree(c->nan_count);
-        if (c->nan_list) (void)hipFree(c->nan_list);
-        if (c->sample_count) (void)hipFree(c->sample_count);
-        if (c->estimate_host) (void)hipHostFree(c->estimate_host);
-        c->young_masks = nullptr; c->young_list = nullptr; c->young_count = nullptr; c->nan_count = nullptr; c->nan_list = nullptr;
-        c->sample_count = nullptr; c->estimate_host = nullptr;
-    };
-    drop();
+    // all or none: the set is built aside and taken over whole, so a failed allocation leaves nothing behind that a later call would
+    // mistake for a complete set
+    DevicePtr<unsigned long long> young_masks, young_count, sample_count;
+    DevicePtr<uint32_t> young_list, nan_list;
+    DevicePtr<unsigned> nan_count;
+    HostPtr<unsigned long long> estimate_host;
     const size_t nmasks = (size_t)c->strip.rows * ((c->W + 63) / 64);
-    hipError_t e = hipMalloc((void**)&c->young_masks, nmasks * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(c->young_masks, 0, nmasks * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->young_list, svgf::young_list_entries(c->strip.rows, c->W) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->young_count, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(c->young_count, 0, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->nan_count, 2 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemsetAsync(c->nan_count, 0, 2 * sizeof(unsigned), c->stream);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->nan_list, (size_t)svgf::kNanListCap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->sample_count, 32 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(c->sample_count, 0, 32 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->estimate_host, 64, hipHostMallocMapped);
-    if (e == hipSuccess) { c->estimate_host[0] = 0ull; c->dense_moments = false; }
-    if (e != hipSuccess) { drop(); return hip_fail(c, e, "alloc_flags"); }
+    hipError_t e = acquire(young_masks, hipMalloc<unsigned long long>, nmasks * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(young_masks.get(), 0, nmasks * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = acquire(young_list, hipMalloc<uint32_t>, svgf::young_list_entries(c->strip.rows, c->W) * sizeof(uint32_t));
+    if (e == hipSuccess) e = acquire(young_count, hipMalloc<unsigned long long>, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(young_count.get(), 0, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = acquire(nan_count, hipMalloc<unsigned>, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemsetAsync(nan_count.get(), 0, 2 * sizeof(unsigned), c->stream);
+    if (e == hipSuccess) e = acquire(nan_list, hipMalloc<uint32_t>, (size_t)svgf::kNanListCap * sizeof(uint32_t));
+    if (e == hipSuccess) e = acquire(sample_count, hipMalloc<unsigned long long>, 32 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(sample_count.get(), 0, 32 * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = acquire(estimate_host, hipHostMalloc<unsigned long long>, 64, hipHostMallocMapped);
+    if (e != hipSuccess) return hip_fail(c, e, "alloc_flags");
+    *estimate_host = 0ull;
+    c->young_masks = std::move(young_masks); c->young_list = std::move(young_list); c->young_count = std::move(young_count);
+    c->nan_count = std::move(nan_count); c->nan_list = std::move(nan_list); c->sample_count = std::move(sample_count);
+    c->estimate_host = std::move(estimate_host);
+    c->dense_moments = false;
     c->young_phase = 0;
     c->young_pending = false;
     return SVGF_OK;
@@ -142,21 +139,28 @@ int alloc_halo_counter(svgf_ctx* c) {
     unsigned long long cap = 0;
     if (int rc = capture_of(c, &cap); rc != SVGF_OK) return rc;
     if (cap) return fail(c, SVGF_ERR_INVALID, "the context's stream is being captured and a strip context's first temporal launch allocates: enqueue one before the capture begins");
-    SVGF_HIP(c, hipMalloc((void**)&c->halo_violations, sizeof(unsigned)));
-    SVGF_HIP(c, hipMemsetAsync(c->halo_violations, 0, sizeof(unsigned), c->stream));
+    SVGF_HIP(c, acquire(c->halo_violations, hipMalloc<unsigned>, sizeof(unsigned)));
+    SVGF_HIP(c, hipMemsetAsync(c->halo_violations.get(), 0, sizeof(unsigned), c->stream));
     return SVGF_OK;
 }
 
 int alloc_state(svgf_ctx* c) {
     if (c->have_state) return SVGF_OK;
+    // all or none, like alloc_flags: the planes are taken over only once every one of them exists
+    DevicePtr<void> colour[2], moments[2], filter[2], guide, guide_prev;
+    DevicePtr<uint8_t> hist[2];
     for (int i = 0; i < 2; i++) {
-        SVGF_HIP(c, hipMalloc(&c->colour[i], colour_bytes(c)));
-        SVGF_HIP(c, hipMalloc(&c->moments[i], moments_bytes(c)));
-        SVGF_HIP(c, hipMalloc(&c->filter[i], colour_bytes(c)));
-        SVGF_HIP(c, hipMalloc((void**)&c->hist[i], hist_bytes(c)));
+        SVGF_HIP(c, acquire(colour[i], hipMalloc<void>, colour_bytes(c)));
+        SVGF_HIP(c, acquire(moments[i], hipMalloc<void>, moments_bytes(c)));
+        SVGF_HIP(c, acquire(filter[i], hipMalloc<void>, colour_bytes(c)));
+        SVGF_HIP(c, acquire(hist[i], hipMalloc<uint8_t>, hist_bytes(c)));
     }
-    SVGF_HIP(c, hipMalloc(&c->guide, (size_t)c->strip.rows * c->W * 16));
-    SVGF_HIP(c, hipMalloc(&c->guide_prev, (size_t)c->strip.rows * c->W * 16));
+    SVGF_HIP(c, acquire(guide, hipMalloc<void>, (size_t)c->strip.rows * c->W * 16));
+    SVGF_HIP(c, acquire(guide_prev, hipMalloc<void>, (size_t)c->strip.rows * c->W * 16));
+    for (int i = 0; i < 2; i++) {
+        c->colour[i] = std::move(colour[i]); c->moments[i] = std::move(moments[i]); c->filter[i] = std::move(filter[i]); c->hist[i] = std::move(hist[i]);
+    }
+    c->guide = std::move(guide); c->guide_prev = std::move(guide_prev);
     c->guide_prev_valid = false;
     c->have_state = true;
     return reset_history(c);
@@ -166,8 +170,8 @@ int alloc_state(svgf_ctx* c) {
 int alloc_alt(svgf_ctx* c) {
     if (c->frames_in_flight < 2 || (c->filter_alt[0] && c->filter_alt[1])) return SVGF_OK;
     for (int i = 0; i < 2; i++) {
-        if (!c->filter_alt[i]) SVGF_HIP(c, hipMalloc(&c->filter_alt[i], colour_bytes(c)));
-        SVGF_HIP(c, hipMemsetAsync(c->filter_alt[i], 0, colour_bytes(c), c->stream));
+        if (!c->filter_alt[i]) SVGF_HIP(c, acquire(c->filter_alt[i], hipMalloc<void>, colour_bytes(c)));
+        SVGF_HIP(c, hipMemsetAsync(c->filter_alt[i].get(), 0, colour_bytes(c), c->stream));
     }
     return SVGF_OK;
 }
@@ -181,36 +185,10 @@ int join_side(svgf_ctx* c, hipStream_t onto) {
         if (int rc = capture_of(c, &cap); rc != SVGF_OK) return rc;
         if (cap != c->in_flight_capture) { c->in_flight = false; c->in_flight_capture = 0; return SVGF_OK; }
     }
-    SVGF_HIP(c, hipStreamWaitEvent(onto, c->ev_done, 0));
+    SVGF_HIP(c, hipStreamWaitEvent(onto, c->ev_done.get(), 0));
     c->in_flight = false;
     c->in_flight_capture = 0;
     return SVGF_OK;
-}
-
-void free_state(svgf_ctx* c) {
-    for (int i = 0; i < 2; i++) {
-        if (c->colour[i]) (void)hipFree(c->colour[i]);
-        if (c->moments[i]) (void)hipFree(c->moments[i]);
-        if (c->filter[i]) (void)hipFree(c->filter[i]);
-        if (c->hist[i]) (void)hipFree(c->hist[i]);
-        if (c->filter_alt[i]) (void)hipFree(c->filter_alt[i]);
-        c->colour[i] = c->moments[i] = c->filter[i] = c->filter_alt[i] = nullptr;
-        c->hist[i] = nullptr;
-    }
-    if (c->guide) (void)hipFree(c->guide);
-    if (c->guide_prev) (void)hipFree(c->guide_prev);
-    c->guide = c->guide_prev = nullptr;
-    c->guide_prev_valid = false;
-    if (c->young_masks) (void)hipFree(c->young_masks);
-    if (c->young_list) (void)hipFree(c->young_list);
-    if (c->young_count) (void)hipFree(c->young_count);
-    if (c->nan_count) (void)hipFree(c->nan_count);
-    if (c->nan_list) (void)hipFree(c->nan_list);
-    if (c->sample_count) (void)hipFree(c->sample_count);
-    if (c->estimate_host) (void)hipHostFree(c->estimate_host);
-    c->young_masks = nullptr; c->young_list = nullptr; c->young_count = nullptr; c->nan_count = nullptr; c->nan_list = nullptr;
-    c->sample_count = nullptr; c->estimate_host = nullptr;
-    c->have_state = false;
 }
 
 int reset_history(svgf_ctx* c) {
@@ -218,11 +196,11 @@ int reset_history(svgf_ctx* c) {
     int rc = join_side(c, c->stream);             // the frame in flight still writes filter planes
     if (rc != SVGF_OK) return rc;
     for (int i = 0; i < 2; i++) {
-        SVGF_HIP(c, hipMemsetAsync(c->colour[i], 0, colour_bytes(c), c->stream));
-        SVGF_HIP(c, hipMemsetAsync(c->moments[i], 0, moments_bytes(c), c->stream));
-        SVGF_HIP(c, hipMemsetAsync(c->filter[i], 0, colour_bytes(c), c->stream));
-        if (c->filter_alt[i]) SVGF_HIP(c, hipMemsetAsync(c->filter_alt[i], 0, colour_bytes(c), c->stream));
-        SVGF_HIP(c, hipMemsetAsync(c->hist[i], 0, hist_bytes(c), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(c->colour[i].get(), 0, colour_bytes(c), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(c->moments[i].get(), 0, moments_bytes(c), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(c->filter[i].get(), 0, colour_bytes(c), c->stream));
+        if (c->filter_alt[i]) SVGF_HIP(c, hipMemsetAsync(c->filter_alt[i].get(), 0, colour_bytes(c), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(c->hist[i].get(), 0, hist_bytes(c), c->stream));
     }
     c->pingpong = 0;
     c->frames_since_reset = 0;
@@ -236,9 +214,9 @@ int read_halo_violations(svgf_ctx* c, unsigned long long* count, int clear) {
     *count = 0;
     if (!c->halo_violations) return SVGF_OK;
     unsigned v = 0;
-    SVGF_HIP(c, hipMemcpyAsync(&v, c->halo_violations, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    SVGF_HIP(c, hipMemcpyAsync(&v, c->halo_violations.get(), sizeof(v), hipMemcpyDeviceToHost, c->stream));
     SVGF_HIP(c, hipStreamSynchronize(c->stream));
-    if (clear && v) SVGF_HIP(c, hipMemsetAsync(c->halo_violations, 0, sizeof(unsigned), c->stream));
+    if (clear && v) SVGF_HIP(c, hipMemsetAsync(c->halo_violations.get(), 0, sizeof(unsigned), c->stream));
     *count = v;
     return SVGF_OK;
 }
@@ -255,25 +233,25 @@ int temporal_impl(svgf_ctx* c, const void* prev_colour, const void* radiance, vo
     if (prev_colour == colour_out || hist_prev == hist_cur || moments_prev == moments_cur)
         return fail(c, SVGF_ERR_INVALID, "svgf_temporal: previous and current state planes must differ (App. B #1)");
     if (passthrough_out && c->young_pending) {      // the lists of an earlier launch were never consumed (an error in between): start them again
-        SVGF_HIP(c, hipMemsetAsync(c->young_count + c->young_phase * svgf::kYoungCounterStride, 0, svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream));
-        SVGF_HIP(c, hipMemsetAsync(c->nan_count + c->young_phase, 0, sizeof(unsigned), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(c->young_count.get() + c->young_phase * svgf::kYoungCounterStride, 0, svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(c->nan_count.get() + c->young_phase, 0, sizeof(unsigned), c->stream));
     }
     svgf::TemporalArgs a{prev_colour, radiance, colour_out,
                          (const float4*)cur->motion, (const uint2*)cur->normal, (const uint2*)cur->uv,
                          (const float4*)prev->motion, (const uint2*)prev->normal, (const uint2*)prev->uv,
                          hist_prev, hist_cur, moments_cur, moments_prev,
                          c->p.depth_threshold, c->p.normal_threshold, c->p.history_base, c->p.mesh_id_test, passthrough_out,
-                         passthrough_out ? c->young_masks : nullptr, passthrough_out && !c->dense_now ? c->young_list : nullptr,
-                         passthrough_out ? c->young_count + c->young_phase * svgf::kYoungCounterStride : nullptr,
-                         passthrough_out ? c->young_count + (c->young_phase ^ 1) * svgf::kYoungCounterStride : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
-                         sparse_colour, c->p.phi_normal > 0.0f, c->halo_violations,
+                         passthrough_out ? c->young_masks.get() : nullptr, passthrough_out && !c->dense_now ? c->young_list.get() : nullptr,
+                         passthrough_out ? c->young_count.get() + c->young_phase * svgf::kYoungCounterStride : nullptr,
+                         passthrough_out ? c->young_count.get() + (c->young_phase ^ 1) * svgf::kYoungCounterStride : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
+                         sparse_colour, c->p.phi_normal > 0.0f, c->halo_violations.get(),
                          std::max(c->vy0, c->strip.y0) - c->strip.y0, std::min(c->vy1, c->strip.y0 + c->strip.rows) - c->strip.y0, (uint4*)guide_out,
                          (const uint4*)guide_prev,
                          c->strip.y0, c->strip.y0 + c->strip.rows,       // the guide texels of every row held (a strip runs the stage on fewer)
-                         passthrough_out ? c->nan_list : nullptr, passthrough_out ? c->nan_count + c->young_phase : nullptr,
-                         passthrough_out ? c->nan_count + (c->young_phase ^ 1) : nullptr,
-                         passthrough_out ? c->sample_count + c->young_phase * 16 : nullptr, passthrough_out ? c->sample_count + (c->young_phase ^ 1) * 16 : nullptr,
-                         passthrough_out ? c->estimate_host : nullptr, c->cold_now, c->p.nan_policy == SVGF_NAN_ZERO};
+                         passthrough_out ? c->nan_list.get() : nullptr, passthrough_out ? c->nan_count.get() + c->young_phase : nullptr,
+                         passthrough_out ? c->nan_count.get() + (c->young_phase ^ 1) : nullptr,
+                         passthrough_out ? c->sample_count.get() + c->young_phase * 16 : nullptr, passthrough_out ? c->sample_count.get() + (c->young_phase ^ 1) * 16 : nullptr,
+                         passthrough_out ? c->estimate_host.get() : nullptr, c->cold_now, c->p.nan_policy == SVGF_NAN_ZERO};
     if (c->re <= c->rb) return SVGF_OK;             // nothing to launch: the young masks and the counters stay as they are
     SVGF_HIP(c, svgf::launch_temporal(geo_of(c), c->p.storage, a, c->stream));
     if (passthrough_out) c->young_pending = true;
@@ -289,8 +267,8 @@ int moments_impl(svgf_ctx* c, const void* colour, void* out, const void* moments
     if (rc != SVGF_OK) return rc;
     svgf::MomentsArgs a{colour, out, moments, (const float4*)g->motion, (const uint2*)g->normal, hist,
                         c->p.phi_colour, c->p.phi_normal, c->p.moments_radius, cold_only, dense, sparse_colour,
-                        cold_only ? c->young_masks : nullptr, cold_only ? c->young_list : nullptr, cold_only ? c->young_count + c->young_phase * svgf::kYoungCounterStride : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
-                        cold_only ? c->nan_list : nullptr, cold_only ? c->nan_count + c->young_phase : nullptr,
+                        cold_only ? c->young_masks.get() : nullptr, cold_only ? c->young_list.get() : nullptr, cold_only ? c->young_count.get() + c->young_phase * svgf::kYoungCounterStride : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
+                        cold_only ? c->nan_list.get() : nullptr, cold_only ? c->nan_count.get() + c->young_phase : nullptr,
                         c->p.variant == SVGF_VARIANT_LDS_GENERAL};
     if (c->re <= c->rb) {
         // No moments rows.  If the temporal launch of this frame did run (young_pending), its list is dropped: the counter pair still
@@ -316,7 +294,7 @@ const void* prev_guide_for(const svgf_ctx* c, const svgf_gbuffer* cur, const svg
     const svgf_gbuffer& k = c->guide_prev_of;
     if (prev->motion != k.motion || prev->normal != k.normal || prev->uv != k.uv) return nullptr;
     if (prev->motion == cur->motion || prev->normal == cur->normal || prev->uv == cur->uv) return nullptr;
-    return c->guide_prev;
+    return c->guide_prev.get();
 }
 
 void commit_guide(svgf_ctx* c, const svgf_gbuffer* cur, bool written) {
@@ -331,7 +309,7 @@ static unsigned long long* path_stats_of(const svgf_ctx* c, int step) {
     if (!c->path_stats || step < 1 || (step & (step - 1)) != 0) return nullptr;
     int i = 0;
     while ((1 << i) < step) i++;
-    return i < SVGF_PATH_STAT_STEPS ? c->path_stats + 2 * i : nullptr;
+    return i < SVGF_PATH_STAT_STEPS ? c->path_stats.get() + 2 * i : nullptr;
 }
 
 int atrous_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide) {
@@ -405,7 +383,7 @@ void choose_moments_kernel(svgf_ctx* c, bool* cold, bool* crowded) {
     *cold = c->frames_since_reset < 3 && streams;
     *crowded = false;
     if (!*cold && c->adaptive_moments && c->estimate_host && streams && c->p.moments_radius == 3 && c->re > c->rb) {
-        const unsigned long long sample = *(volatile unsigned long long*)c->estimate_host;   // {waves that hold some young pixels: high word, young pixels: low word}, of one wave in 64
+        const unsigned long long sample = *(volatile unsigned long long*)c->estimate_host.get();   // {waves that hold some young pixels: high word, young pixels: low word}, of one wave in 64
         const double est = 64.0 * (double)(unsigned)sample / ((double)c->W * (double)(c->re - c->rb));
         const unsigned long long appends = 64ull * (sample >> 32), cap = svgf::young_append_cap(c->strip.rows, c->W);   // what the list of such a frame takes, and its cap
         if (est > 0.08 || appends > cap) c->dense_moments = true;
@@ -498,26 +476,12 @@ int svgf_create(svgf_ctx** out, int width, int height, const svgf_params* params
     return svgf_create_strip(out, width, height, &s, params, device, hip_stream);
 }
 
-// the side stream and its events (frames_in_flight back to 1, destruction); waits for what is on it
-static void drop_side(svgf_ctx* c) {
-    if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); c->side = nullptr; }
-    if (c->ev_first) { (void)hipEventDestroy(c->ev_first); c->ev_first = nullptr; }
-    if (c->ev_done) { (void)hipEventDestroy(c->ev_done); c->ev_done = nullptr; }
-
-    c->in_flight = false;
-}
-
 void svgf_destroy(svgf_ctx* c) {
     if (!c || c->strip_drv) return;            // a context handed out by svgf_strips_context belongs to its strip driver (svgf_strips_destroy)
     DeviceGuard dg(c->device);
     if (c->have_state || !c->pool.empty() || !c->pending.empty() || c->halo_violations) (void)hipStreamSynchronize(c->stream);
-    drop_side(c);
-    free_state(c);
-    if (c->halo_violations) (void)hipFree(c->halo_violations);
-    if (c->path_stats) (void)hipFree(c->path_stats);
-    for (auto& f : c->pending) for (auto e : f.ev) (void)hipEventDestroy(e);
-    for (auto e : c->pool) (void)hipEventDestroy(e);
-    delete c;
+    if (c->side) (void)hipStreamSynchronize(c->side.get());
+    delete c;                                  // (its handles release what it owns, on this device)
 }
 
 // application::ResizeRenderTextures (App.cu:742-778): the render size changed, every filter buffer is reallocated and the
@@ -529,10 +493,13 @@ int svgf_resize_strip(svgf_ctx* c, int width, int height, const svgf_strip* stri
     if (c->strip_drv) return fail(c, SVGF_ERR_INVALID, "svgf_resize: this context belongs to a strip driver: svgf_strips_destroy it and create one for the new size");
     DeviceGuard dg(c->device);
     SVGF_HIP(c, hipStreamSynchronize(c->stream));        // cudaDeviceSynchronize() in the reference (App.cu:758)
-    if (c->side) SVGF_HIP(c, hipStreamSynchronize(c->side));
+    if (c->side) SVGF_HIP(c, hipStreamSynchronize(c->side.get()));
     c->in_flight = false;
-    free_state(c);
-    if (c->halo_violations) { (void)hipFree(c->halo_violations); c->halo_violations = nullptr; }
+    for (int i = 0; i < 2; i++) { c->colour[i].reset(); c->moments[i].reset(); c->filter[i].reset(); c->hist[i].reset(); c->filter_alt[i].reset(); }
+    c->guide.reset(); c->guide_prev.reset();
+    c->young_masks.reset(); c->young_list.reset(); c->young_count.reset(); c->nan_count.reset(); c->nan_list.reset(); c->sample_count.reset();
+    c->estimate_host.reset(); c->halo_violations.reset();
+    c->have_state = false; c->guide_prev_valid = false;
     c->W = width; c->H = height; c->strip = *strip; c->rb = strip->own_begin; c->re = strip->own_end;
     c->vy0 = strip->y0; c->vy1 = strip->y0 + strip->rows;
     c->pingpong = 0; c->frames_since_reset = 0; c->result_index = 0; c->filter_set = 0; c->last_pair_alt = false;
@@ -605,7 +572,7 @@ int svgf_adaptive_moments_state(const svgf_ctx* c) { return c && c->dense_moment
 
 int svgf_adaptive_moments_sample(const svgf_ctx* c, unsigned* young_pixels, unsigned* appending_waves) {
     if (!c || !c->estimate_host) return SVGF_ERR_INVALID;
-    const unsigned long long sample = *(volatile unsigned long long*)c->estimate_host;
+    const unsigned long long sample = *(volatile unsigned long long*)c->estimate_host.get();
     auto sat = [](unsigned long long v) { return v > 0xffffffffull ? 0xffffffffu : (unsigned)v; };
     if (young_pixels) *young_pixels = sat(64ull * (sample & 0xffffffffull));
     if (appending_waves) *appending_waves = sat(64ull * (sample >> 32));
@@ -668,9 +635,9 @@ int svgf_set_frames_in_flight(svgf_ctx* c, int frames) {
     if (frames == 2 && c->debug_mode != SVGF_DEBUG_FINAL) return fail(c, SVGF_ERR_INVALID, "svgf_set_frames_in_flight: not with a debug view selected");
     DeviceGuard dg(c->device);
     if (frames == 2) {
-        if (!c->side) SVGF_HIP(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-        if (!c->ev_first) SVGF_HIP(c, hipEventCreateWithFlags(&c->ev_first, hipEventDisableTiming));
-        if (!c->ev_done) SVGF_HIP(c, hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming));
+        if (!c->side) SVGF_HIP(c, acquire(c->side, hipStreamCreateWithFlags, hipStreamNonBlocking));
+        if (!c->ev_first) SVGF_HIP(c, acquire(c->ev_first, hipEventCreateWithFlags, hipEventDisableTiming));
+        if (!c->ev_done) SVGF_HIP(c, acquire(c->ev_done, hipEventCreateWithFlags, hipEventDisableTiming));
     } else {
         int rc = join_side(c, c->stream);
         if (rc != SVGF_OK) return rc;
@@ -802,7 +769,7 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     if (rc != SVGF_OK) return rc;
     const int P = c->pingpong;
     // frames in flight: this frame's pair of filter planes (the previous frame's result sits in the other one until the call after this)
-    void** const F = c->frames_in_flight > 1 && c->filter_set ? c->filter_alt : c->filter;
+    const DevicePtr<void>* const F = c->frames_in_flight > 1 && c->filter_set ? c->filter_alt : c->filter;
     c->last_pair_alt = F == c->filter_alt;
     if (c->frames_in_flight > 1) c->filter_set ^= 1;
 
@@ -810,12 +777,12 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     const bool timed = !cap && c->timing > 0 && (c->timing_phase++ % c->timing) == 0;     // (events of a captured frame are graph nodes: nothing to read back)
     auto stamp = [&]() {                            // on c->stream AS IT IS when called (the side stream for the tail of a frame in flight)
         if (!timed) return;
-        hipEvent_t e = take_event(c);
-        if (e && hipEventRecord(e, c->stream) == hipSuccess) fe.ev.push_back(e);
-        else if (e) c->pool.push_back(e);
+        Event e = take_event(c);
+        if (e && hipEventRecord(e.get(), c->stream) == hipSuccess) fe.ev.push_back(std::move(e));
+        else if (e) c->pool.push_back(std::move(e));
     };
     auto bail = [&](int code) {                     // an error path hands the events already taken back to the pool
-        for (auto e : fe.ev) c->pool.push_back(e);
+        for (auto& e : fe.ev) c->pool.push_back(std::move(e));
         fe.ev.clear();
         if (code != SVGF_OK) c->guide_prev_valid = false;      // a frame that failed half-way leaves no guide plane to trust
         return code;
@@ -826,20 +793,20 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         // SVGFDebugOutput::TemporalFilter (App.cu:602-609): the temporal stage alone, its result is the frame.
         // SVGFDebugOutput::ATrousWaveletFilter / Depth (App.cu:611-620, 632-638): temporal, then the wavelet filter WITHOUT
         // FilterMoments — FilterBuffer[0] still holds the previous frame's result (App. B #11), which is what gets filtered.
-        rc = temporal_impl(c, c->colour[1 - P], radiance, c->colour[P], cur, prev, c->hist[1 - P], c->hist[P], c->moments[P], c->moments[1 - P], nullptr, 0);
+        rc = temporal_impl(c, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(), c->moments[P].get(), c->moments[1 - P].get(), nullptr, 0);
         if (rc != SVGF_OK) return bail(rc);
         stamp(); stamp();
-        const void* res = c->colour[P];
+        const void* res = c->colour[P].get();
         if (c->debug_mode == SVGF_DEBUG_ATROUS) {
             int pp = c->result_index;
             for (int i = 0; i < c->p.steps; i++) {
-                rc = atrous_impl(c, c->filter[pp], c->filter[1 - pp], c->colour[P], cur, 1 << i, i);
+                rc = atrous_impl(c, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i);
                 if (rc != SVGF_OK) return bail(rc);
                 stamp();
                 pp ^= 1;
             }
             c->result_index = pp;
-            res = c->filter[pp];
+            res = c->filter[pp].get();
         }
         if (timed) {
             fe.nstage = (int)fe.ev.size() - 1;
@@ -865,14 +832,14 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     // temporal launch lost — since the NEXT frame's reprojection test reads the plane too (below) it pays there as well: -5.7 %)
     // ... and the NEXT frame's reprojection test reads this frame's guide plane instead of the three planes of its previous
     // G-buffer (prev_guide_for): -16 B/px of the temporal launch's 146
-    void* guide = use_guide(c) ? c->guide : nullptr;
-    rc = temporal_impl(c, c->colour[1 - P], radiance, c->colour[P], cur, prev, c->hist[1 - P], c->hist[P],
-                       c->moments[P], c->moments[1 - P], F[0], sparse, guide, prev_guide_for(c, cur, prev));  // App.cu:552
+    void* guide = use_guide(c) ? c->guide.get() : nullptr;
+    rc = temporal_impl(c, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(),
+                       c->moments[P].get(), c->moments[1 - P].get(), F[0].get(), sparse, guide, prev_guide_for(c, cur, prev));  // App.cu:552
     c->dense_now = c->cold_now = false;             // (the stage calls on this context keep their lists)
     if (rc != SVGF_OK) return bail(rc);
     stamp();
     // the first three frames after a reset have history <= 3 everywhere: the LDS-streaming moments kernel
-    rc = moments_impl(c, c->colour[P], F[0], c->moments[P], cur, c->hist[P], 1, cold || crowded, sparse);   // App.cu:554 (current moments: App. B #4)
+    rc = moments_impl(c, c->colour[P].get(), F[0].get(), c->moments[P].get(), cur, c->hist[P].get(), 1, cold || crowded, sparse);   // App.cu:554 (current moments: App. B #4)
     if (rc != SVGF_OK) return bail(rc);
     stamp();
     int pp = 0, first = 0;
@@ -885,23 +852,23 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     auto go_aside = [&]() -> int {
         // the rest of this frame goes onto the side stream; the frame that was there is ordered on the caller's stream first (its
         // result may be consumed, its planes reused)
-        hipError_t e = hipEventRecord(c->ev_first, caller_stream);
+        hipError_t e = hipEventRecord(c->ev_first.get(), caller_stream);
         if (e != hipSuccess) return hip_fail(c, e, "hipEventRecord");
         int r = join_side(c, caller_stream);
         if (r != SVGF_OK) return r;
-        e = hipStreamWaitEvent(c->side, c->ev_first, 0);
+        e = hipStreamWaitEvent(c->side.get(), c->ev_first.get(), 0);
         if (e != hipSuccess) return hip_fail(c, e, "hipStreamWaitEvent");
-        c->stream = c->side;
+        c->stream = c->side.get();
         aside = true;
         stamp();                                                                // the tail's own start: it may have waited for the frame before it
         return SVGF_OK;
     };
     if (pair) {
         // iterations 0 and 1 as one launch: F[0] -> F[1] (iteration 0's own plane is never written), feedback as ever
-        rc = atrous_pair_impl(c, F[0], F[1], c->colour[P], cur, guide);
+        rc = atrous_pair_impl(c, F[0].get(), F[1].get(), c->colour[P].get(), cur, guide);
         if (rc == SVGF_OK) { stamp(); stamp(); pp = 1; first = 2; }             // timing slot 2 holds the pair, slot 3 (next to) nothing
     } else if (c->p.steps >= 1) {
-        rc = atrous_impl(c, F[0], F[1], c->colour[P], cur, 1, 0, guide);        // App.cu:497-507, iteration 0: feeds the history back
+        rc = atrous_impl(c, F[0].get(), F[1].get(), c->colour[P].get(), cur, 1, 0, guide);        // App.cu:497-507, iteration 0: feeds the history back
         if (rc == SVGF_OK) { stamp(); pp = 1; first = 1; }
     }
     // Everything the NEXT frame's temporal launch reads is written now: with two frames in flight the remaining iterations leave the
@@ -917,12 +884,12 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         else rc = join_side(c, caller_stream);
     }
     for (int i = first; i < c->p.steps && rc == SVGF_OK; i++) {
-        rc = atrous_impl(c, F[pp], F[1 - pp], c->colour[P], cur, 1 << i, i, guide);
+        rc = atrous_impl(c, F[pp].get(), F[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i, guide);
         if (rc == SVGF_OK) { stamp(); pp ^= 1; }
     }
     if (aside) {
         // (also after a failed launch: whatever did get onto the side stream must be waited for before its planes are touched again)
-        hipError_t e = hipEventRecord(c->ev_done, c->side);
+        hipError_t e = hipEventRecord(c->ev_done.get(), c->side.get());
         if (e == hipSuccess) { c->in_flight = true; c->in_flight_capture = cap; } else if (rc == SVGF_OK) rc = hip_fail(c, e, "hipEventRecord");
         c->stream = caller_stream;
     }
@@ -932,7 +899,7 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         if ((int)fe.ev.size() == fe.nstage + 1 + (aside ? 1 : 0)) c->pending.push_back(std::move(fe));
         else bail(0);
     }
-    if (result) *result = F[pp];
+    if (result) *result = F[pp].get();
     c->result_index = pp;
     commit_guide(c, cur, guide != nullptr);
     c->pingpong ^= 1;                                                           // App.cu:374
@@ -943,10 +910,10 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
 void* svgf_state_plane(svgf_ctx* c, int plane, int index) {
     if (!c || !c->have_state || index < 0 || index > 1) return nullptr;
     switch (plane) {
-        case SVGF_PLANE_COLOUR: return c->colour[index];
-        case SVGF_PLANE_MOMENTS: return c->moments[index];
-        case SVGF_PLANE_FILTER: return c->filter[index];
-        case SVGF_PLANE_HISTORY: return c->hist[index];
+        case SVGF_PLANE_COLOUR: return c->colour[index].get();
+        case SVGF_PLANE_MOMENTS: return c->moments[index].get();
+        case SVGF_PLANE_FILTER: return c->filter[index].get();
+        case SVGF_PLANE_HISTORY: return c->hist[index].get();
         default: return nullptr;
     }
 }
@@ -997,14 +964,11 @@ int svgf_path_stats_enable(svgf_ctx* c, int on) {
     if (!c) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
     SVGF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->side) SVGF_HIP(c, hipStreamSynchronize(c->side));
+    if (c->side) SVGF_HIP(c, hipStreamSynchronize(c->side.get()));
     if (on && !c->path_stats) {
-        SVGF_HIP(c, hipMalloc((void**)&c->path_stats, 2 * SVGF_PATH_STAT_STEPS * sizeof(unsigned long long)));
-        SVGF_HIP(c, hipMemset(c->path_stats, 0, 2 * SVGF_PATH_STAT_STEPS * sizeof(unsigned long long)));
-    } else if (!on && c->path_stats) {
-        (void)hipFree(c->path_stats);
-        c->path_stats = nullptr;
-    }
+        SVGF_HIP(c, acquire(c->path_stats, hipMalloc<unsigned long long>, 2 * SVGF_PATH_STAT_STEPS * sizeof(unsigned long long)));
+        SVGF_HIP(c, hipMemset(c->path_stats.get(), 0, 2 * SVGF_PATH_STAT_STEPS * sizeof(unsigned long long)));
+    } else if (!on) c->path_stats.reset();
     return SVGF_OK;
 }
 
@@ -1013,10 +977,10 @@ int svgf_path_stats_read(svgf_ctx* c, unsigned long long* counts, int slots) {
     if (!c->path_stats) return fail(c, SVGF_ERR_INVALID, "svgf_path_stats_read: not enabled (svgf_path_stats_enable)");
     DeviceGuard dg(c->device);
     SVGF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->side) SVGF_HIP(c, hipStreamSynchronize(c->side));
+    if (c->side) SVGF_HIP(c, hipStreamSynchronize(c->side.get()));
     unsigned long long h[2 * SVGF_PATH_STAT_STEPS];
-    SVGF_HIP(c, hipMemcpy(h, c->path_stats, sizeof(h), hipMemcpyDeviceToHost));
-    SVGF_HIP(c, hipMemset(c->path_stats, 0, sizeof(h)));
+    SVGF_HIP(c, hipMemcpy(h, c->path_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
+    SVGF_HIP(c, hipMemset(c->path_stats.get(), 0, sizeof(h)));
     for (int i = 0; i < slots; i++) counts[i] = i < 2 * SVGF_PATH_STAT_STEPS ? h[i] : 0ull;
     return SVGF_OK;
 }
@@ -1031,18 +995,21 @@ int svgf_timing_enable(svgf_ctx* c, int on) {
 int svgf_timing_read(svgf_ctx* c, double* ms_sum, int* frames, int slots) {
     if (!c || !ms_sum || slots <= 0) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
-    for (auto& f : c->pending) {
-        SVGF_HIP(c, hipEventSynchronize(f.ev.back()));
+    // a frame leaves `pending` (its events back to the pool, its times into the sums) only once all of it has been read: a failure
+    // leaves it and the frames behind it pending
+    while (!c->pending.empty()) {
+        svgf_ctx::FrameEvents& f = c->pending.front();
+        SVGF_HIP(c, hipEventSynchronize(f.ev.back().get()));
+        float ms[2 + SVGF_MAX_STEPS] = {};
         for (int i = 0; i < f.nstage; i++) {
-            float ms = 0.f;
             const int b = i >= f.split ? i + 1 : i;
-            SVGF_HIP(c, hipEventElapsedTime(&ms, f.ev[b], f.ev[b + 1]));
-            c->ms_sum[i] += ms;
+            SVGF_HIP(c, hipEventElapsedTime(&ms[i], f.ev[b].get(), f.ev[b + 1].get()));
         }
-        for (auto e : f.ev) c->pool.push_back(e);
+        for (int i = 0; i < f.nstage; i++) c->ms_sum[i] += ms[i];
+        for (auto& e : f.ev) c->pool.push_back(std::move(e));
+        c->pending.erase(c->pending.begin());
         c->timed_frames++;
     }
-    c->pending.clear();
     for (int i = 0; i < slots; i++) ms_sum[i] = i < 2 + SVGF_MAX_STEPS ? c->ms_sum[i] : 0.0;
     if (frames) *frames = c->timed_frames;
     std::memset(c->ms_sum, 0, sizeof(c->ms_sum));

@@ -6,10 +6,36 @@
 #include "../../include/svgf_test.h"
 #include "svgf_kernels.h"
 
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 struct svgf_strip_driver;
+
+namespace svgf_host {
+
+// Owning handles: every device buffer, host-mapped word, stream and event the library creates has exactly one of these as its owner,
+// and the owner's destruction (or reset, or a move onto it) is the one place it is released.
+struct FreeDevice { void operator()(void* p) const { (void)hipFree(p); } };
+struct FreeHost { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct DestroyEvent { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+struct DestroyStream { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+template <class T> using DevicePtr = std::unique_ptr<T, FreeDevice>;
+template <class T> using HostPtr = std::unique_ptr<T, FreeHost>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, DestroyEvent>;
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, DestroyStream>;
+
+// make(&tmp, args...) acquires into a temporary (hipMalloc<T>, hipEventCreateWithFlags, ...); `h` takes it, releasing what it held, only on
+// success — a failure leaves `h` as it was
+template <class H, class F, class... A> hipError_t acquire(H& h, F make, A... args) {
+    typename H::pointer p = nullptr;
+    const hipError_t e = make(&p, args...);
+    if (e == hipSuccess) h.reset(p);
+    return e;
+}
+
+}  // namespace svgf_host
 
 #ifndef SVGF_PREV_GUIDE_DEFAULT
 #define SVGF_PREV_GUIDE_DEFAULT 0      // opt-in (svgf_set_prev_guide): it relies on the host not rewriting the previous G-buffer's planes
@@ -29,12 +55,10 @@ struct svgf_ctx {
     std::string err;
     // context-owned state (frame driver): RenderBuffer[2], MomentsBuffer[2], FilterBuffer[2] (App.h:138-140)
     // and the ping-ponged history plane (App.h:141 + SURVEY App. B #1)
-    void* colour[2] = {nullptr, nullptr};
-    void* moments[2] = {nullptr, nullptr};
-    void* filter[2] = {nullptr, nullptr};
-    uint8_t* hist[2] = {nullptr, nullptr};
-    void* guide = nullptr;                 // {depth, ddepth, normal, instance ID} of the current G-buffer repacked by the temporal launch for the wavelet iterations
-    void* guide_prev = nullptr;            // ... and the plane the previous frame wrote (the two swap at the end of a frame): the next reprojection test reads it
+    svgf_host::DevicePtr<void> colour[2], moments[2], filter[2];
+    svgf_host::DevicePtr<uint8_t> hist[2];
+    svgf_host::DevicePtr<void> guide;      // {depth, ddepth, normal, instance ID} of the current G-buffer repacked by the temporal launch for the wavelet iterations
+    svgf_host::DevicePtr<void> guide_prev; // ... and the plane the previous frame wrote (the two swap at the end of a frame): the next reprojection test reads it
     svgf_gbuffer guide_prev_of{};          // the G-buffer guide_prev was made from (the planes' addresses), valid while guide_prev_valid
     bool guide_prev_valid = false;
     bool prev_guide_enabled = SVGF_PREV_GUIDE_DEFAULT != 0;   // svgf_set_prev_guide
@@ -44,42 +68,42 @@ struct svgf_ctx {
     // between two pairs of filter planes (the guide planes alternate anyway), and a frame's result is ordered on `stream` by the next
     // svgf_denoise_frame / svgf_flush / svgf_sync.
     int frames_in_flight = 1;
-    hipStream_t side = nullptr;
-    hipEvent_t ev_first = nullptr, ev_done = nullptr;   // iteration 0 of the frame being enqueued is on `stream`; the last iteration of the frame in flight is on `side`
-    void* filter_alt[2] = {nullptr, nullptr};
+    svgf_host::Stream side;
+    svgf_host::Event ev_first, ev_done;    // iteration 0 of the frame being enqueued is on `stream`; the last iteration of the frame in flight is on `side`
+    svgf_host::DevicePtr<void> filter_alt[2];
     int filter_set = 0;                    // which pair the NEXT frame uses (toggles per frame while frames_in_flight == 2)
     bool last_pair_alt = false;            // the last frame wrote filter_alt[] (under its present name): what svgf_set_frames_in_flight(1) renames
     bool in_flight = false;                // a frame's tail is on `side` and `stream` has not been made to wait for it yet
     unsigned long long in_flight_capture = 0;   // ... and the stream capture that tail was recorded in (0: none; svgf.h, Stream capture)
-    unsigned long long* young_masks = nullptr;   // scratch, temporal -> moments: per (row, 64-column segment) the lanes whose pixel (history < 4) needs the spatial estimate
-    uint32_t* young_list = nullptr;        // ... and the indices of the pixels of the partly young segments (svgf::young_list_entries)
-    unsigned long long* young_count = nullptr;   // ... two {appends, pixels} counters used in turn (the temporal launch of a frame zeroes the next frame's)
-    unsigned* nan_count = nullptr;         // two device counters of nan_list used in turn (the temporal launch of a frame zeroes the next frame's)
-    unsigned long long* sample_count = nullptr;   // two 64-bit device counters (128 B apart) used in turn: the sampled number of young pixels of a frame (TemporalArgs::sample_count)
-    unsigned long long* estimate_host = nullptr;    // host-mapped: the latest sample a temporal launch has published (read without synchronising: some frames old)
+    svgf_host::DevicePtr<unsigned long long> young_masks;   // scratch, temporal -> moments: per (row, 64-column segment) the lanes whose pixel (history < 4) needs the spatial estimate
+    svgf_host::DevicePtr<uint32_t> young_list;   // ... and the indices of the pixels of the partly young segments (svgf::young_list_entries)
+    svgf_host::DevicePtr<unsigned long long> young_count;   // ... two {appends, pixels} counters used in turn (the temporal launch of a frame zeroes the next frame's)
+    svgf_host::DevicePtr<unsigned> nan_count;    // two device counters of nan_list used in turn (the temporal launch of a frame zeroes the next frame's)
+    svgf_host::DevicePtr<unsigned long long> sample_count;   // two 64-bit device counters (128 B apart) used in turn: the sampled number of young pixels of a frame (TemporalArgs::sample_count)
+    svgf_host::HostPtr<unsigned long long> estimate_host;   // host-mapped: the latest sample a temporal launch has published (read without synchronising: some frames old)
     bool adaptive_moments = true;          // svgf_set_adaptive_moments
     bool dense_moments = false;            // the frame driver's current choice (hysteresis)
     bool dense_now = false;                // the frame being enqueued is served by the streaming kernel (a cold or a crowded frame)
     bool cold_now = false;                 // ... it is one of the first three after a reset
-    uint32_t* nan_list = nullptr;          // scratch, temporal -> moments: the pixels whose accumulated colour / moments are NaN or inf (kNanListCap entries)
+    svgf_host::DevicePtr<uint32_t> nan_list;     // scratch, temporal -> moments: the pixels whose accumulated colour / moments are NaN or inf (kNanListCap entries)
     int young_phase = 0;
     bool young_pending = false;            // a temporal launch wrote the masks / appended to nan_count[young_phase] and no moments launch has consumed them yet
     int vy0 = 0, vy1 = 0;                  // global rows of the previous-frame planes that hold valid state (svgf_set_valid_rows; default: all held)
-    unsigned* halo_violations = nullptr;   // strips: device counter of reprojections that left the rows this strip holds (temporal_kernel)
+    svgf_host::DevicePtr<unsigned> halo_violations;   // strips: device counter of reprojections that left the rows this strip holds (temporal_kernel)
     int pingpong = 0;                      // PingPongInx, App.cu:374
     int frames_since_reset = 0;
     int result_index = 0;                  // which filter plane holds the last result (the reference copies it back into FilterBuffer[0], App.cu:510-513)
     int debug_mode = SVGF_DEBUG_FINAL;     // SVGFDebugOutput, App.cu:545-649
     bool have_state = false;
     svgf_strip_driver* strip_drv = nullptr;
-    unsigned long long* path_stats = nullptr;   // svgf_path_stats_enable: device counters, a pair per step 1 << i (svgf_kernels.h: AtrousArgs::path_stats), or null
+    svgf_host::DevicePtr<unsigned long long> path_stats;   // svgf_path_stats_enable: device counters, a pair per step 1 << i (svgf_kernels.h: AtrousArgs::path_stats), or null
     // per-stage timing
     int timing = 0;               // 0 = off, n = stage events on every n-th frame
     int timing_phase = 0;
     // stage i ran between ev[i] and ev[i + 1]; from stage `split` on (the launches on the side stream) between ev[i + 1] and ev[i + 2]
-    struct FrameEvents { std::vector<hipEvent_t> ev; int nstage = 0; int split = 1 << 30; };
-    std::vector<FrameEvents> pending;
-    std::vector<hipEvent_t> pool;
+    struct FrameEvents { std::vector<svgf_host::Event> ev; int nstage = 0; int split = 1 << 30; };
+    std::vector<FrameEvents> pending;      // each event is in exactly one of the two: a frame's events go back to the pool once it has been read
+    std::vector<svgf_host::Event> pool;
     double ms_sum[2 + SVGF_MAX_STEPS] = {0};
     int timed_frames = 0;
 };

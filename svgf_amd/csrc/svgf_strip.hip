@@ -116,16 +116,17 @@ struct svgf_strips {
         int rank = 0, device = 0;
         svgf_ctx* ctx = nullptr;
         ncclComm_t comm = nullptr;
-        hipStream_t compute = nullptr, comm_stream = nullptr;
-        bool own_comm_stream = false;
+        hipStream_t compute = nullptr, comm_stream = nullptr;   // comm_stream: own_comm, or (loop-back ranks k > 0) rank 0's
+        Stream own_comm;
         // svgf_strips_set_frames_in_flight(2): iterations 1.. of a frame run on `side` beside the next frame's temporal launch; `cur` is the stream
         // the launches, the exchanges' ready records and their waits go to at the moment (compute, or side for a frame's tail)
-        hipStream_t side = nullptr, cur = nullptr;
-        hipEvent_t ev_first = nullptr, ev_tail = nullptr;     // iteration 0 of the frame being enqueued is on `compute`; the end of the tail in flight on `side`
+        Stream side;
+        hipStream_t cur = nullptr;
+        Event ev_first, ev_tail;                              // iteration 0 of the frame being enqueued is on `compute`; the end of the tail in flight on `side`
         bool tail_pending = false;                            // ... which `compute` has not been made to wait for yet
-        void* filter_alt[2] = {nullptr, nullptr};
-        hipEvent_t ready = nullptr, halo_done = nullptr, state_done = nullptr;
-        hipEvent_t mb_ready = nullptr, mb_done = nullptr;      // mailbox: this rank's communication stream has reached the group / has received what the group sends it
+        DevicePtr<void> filter_alt[2];
+        Event ready, halo_done, state_done;
+        Event mb_ready, mb_done;                               // mailbox: this rank's communication stream has reached the group / has received what the group sends it
         // edge rows first (svgf_strips_set_edge_first): the iteration in front of an exchange is ONE launch whose first workgroups produce the rows the
         // neighbours wait for; the last of them writes edge_value into its slot's signal word and the communication stream waits for that word
         // (hipStreamWaitValue64) instead of for an event behind two extra launches
@@ -135,18 +136,18 @@ struct svgf_strips {
         // The two signal words are HSA signal memory (hipExtMallocWithFlags(hipMallocSignalMemory): what hipStreamWaitValue64 is documented for; plain
         // device memory works on this ROCm build too — tools/ubench/wait_value.hip — but is not promised), the arrival counters plain device memory.
         // No signal memory: edge_signal stays null and every exchanging iteration keeps the three-launch schedule.
-        unsigned long long* edge_signal[2] = {nullptr, nullptr};
-        unsigned* edge_arrivals = nullptr;                     // two counters, 256 B apart
+        DevicePtr<unsigned long long> edge_signal[2];
+        DevicePtr<unsigned> edge_arrivals;                     // two counters, 256 B apart
         unsigned long long edge_value[2] = {0, 0};
         int edge_slot = 0;                                     // the slot of the launch just enqueued
         bool edge_pending = false;                             // the launch just enqueued signals: the next exchange waits for edge_value[edge_slot]
         bool state_pending = false;
         // the host never runs more than kMaxAhead frames ahead of the device: frame f waits for the end of frame f - kMaxAhead.  With ~100
         // frames of launches, events and RCCL groups queued the device starts to starve (0.43 -> 0.6 ms per 8K/8 strip, tools/strip_sim.py)
-        std::vector<hipEvent_t> frame_done;
+        std::vector<Event> frame_done;
         svgf_strip_plan_geo g;
         // timing of the a-trous launches (bench.py's roofline block at N > 1)
-        std::vector<hipEvent_t> tev;           // pairs
+        std::vector<Event> tev;                // pairs
         std::vector<double> tbytes_px;         // pixels x (1 + feedback) weight per pair: (rows*W, iteration)
         std::vector<int> titer;
     };
@@ -322,19 +323,19 @@ int mb_group_end(svgf_strips* s) {
         if (!taken[k]) return sfail(s, SVGF_ERR_COMM, "mailbox: rank " + std::to_string(s->mb_recvs[k].rank) + " waits for " + std::to_string(s->mb_recvs[k].bytes) + " bytes from rank " +
                                                       std::to_string(s->mb_recvs[k].peer) + ", which sends none in this group: a multi-GPU run would wait here for ever");
     // every rank's communication stream has reached the group (post_exchange made it wait for the rows it sends and the rows it receives into)
-    for (auto& l : s->local) { DeviceGuard dg(l.device); SVGF_SHIP(s, hipEventRecord(l.mb_ready, l.comm_stream)); }
+    for (auto& l : s->local) { DeviceGuard dg(l.device); SVGF_SHIP(s, hipEventRecord(l.mb_ready.get(), l.comm_stream)); }
     std::vector<char> receives(s->world, 0);
     for (const Pair& p : pairs) {
         svgf_strips::Local* src = local_of(s, p.snd->rank);
         svgf_strips::Local* dst = local_of(s, p.rcv->rank);
         DeviceGuard dg(dst->device);
-        SVGF_SHIP(s, hipStreamWaitEvent(dst->comm_stream, src->mb_ready, 0));
+        SVGF_SHIP(s, hipStreamWaitEvent(dst->comm_stream, src->mb_ready.get(), 0));
         if (src->device == dst->device) SVGF_SHIP(s, hipMemcpyAsync(p.rcv->buf, p.snd->buf, p.snd->bytes, hipMemcpyDeviceToDevice, dst->comm_stream));
         else SVGF_SHIP(s, hipMemcpyPeerAsync(p.rcv->buf, dst->device, p.snd->buf, src->device, p.snd->bytes, dst->comm_stream));
         receives[dst->rank] = 1;
         s->mb_copies++; s->mb_bytes += p.snd->bytes;
     }
-    for (auto& l : s->local) if (receives[l.rank]) { DeviceGuard dg(l.device); SVGF_SHIP(s, hipEventRecord(l.mb_done, l.comm_stream)); }
+    for (auto& l : s->local) if (receives[l.rank]) { DeviceGuard dg(l.device); SVGF_SHIP(s, hipEventRecord(l.mb_done.get(), l.comm_stream)); }
     // a send is complete when its buffer may be written again: the sender's stream waits for the copies out of it
     for (auto& l : s->local) {
         std::vector<char> waited(s->world, 0);
@@ -342,7 +343,7 @@ int mb_group_end(svgf_strips* s) {
             if (p.snd->rank != l.rank || waited[p.rcv->rank]) continue;
             waited[p.rcv->rank] = 1;
             DeviceGuard dg(l.device);
-            SVGF_SHIP(s, hipStreamWaitEvent(l.comm_stream, local_of(s, p.rcv->rank)->mb_done, 0));
+            SVGF_SHIP(s, hipStreamWaitEvent(l.comm_stream, local_of(s, p.rcv->rank)->mb_done.get(), 0));
         }
     }
     s->mb_groups++;
@@ -373,13 +374,13 @@ int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, b
     // profiles/r05_strip_trace_*.txt: it is only recorded where something will wait for it.)
     for (auto& l : s->local) {
         DeviceGuard dg(l.device);
-        if (!in_order && !l.edge_pending) SVGF_SHIP(s, hipEventRecord(l.ready, l.cur));
+        if (!in_order && !l.edge_pending) SVGF_SHIP(s, hipEventRecord(l.ready.get(), l.cur));
     }
     // (edge rows first: the rows a rank sends are final when the first workgroups of the launch it has just enqueued have signalled — the
     // communication stream waits for that word, not for the launch; everything enqueued BEFORE that launch is complete by then, stream order)
     auto wait_for = [&](svgf_strips::Local& on, svgf_strips::Local& of) -> int {
-        if (of.edge_pending) SVGF_SHIP(s, hipStreamWaitValue64(on.comm_stream, of.edge_signal[of.edge_slot], of.edge_value[of.edge_slot], hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull));
-        else SVGF_SHIP(s, hipStreamWaitEvent(on.comm_stream, of.ready, 0));
+        if (of.edge_pending) SVGF_SHIP(s, hipStreamWaitValue64(on.comm_stream, of.edge_signal[of.edge_slot].get(), of.edge_value[of.edge_slot], hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull));
+        else SVGF_SHIP(s, hipStreamWaitEvent(on.comm_stream, of.ready.get(), 0));
         return SVGF_OK;
     };
     if (!in_order) for (auto& l : s->local) {
@@ -421,7 +422,7 @@ int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, b
     if (int rc = T.group_end(s); rc != SVGF_OK) { s->broken = true; return rc; }
     for (auto& l : s->local) {
         DeviceGuard dg(l.device);
-        SVGF_SHIP(s, hipEventRecord(is_state ? l.state_done : l.halo_done, l.comm_stream));
+        SVGF_SHIP(s, hipEventRecord((is_state ? l.state_done : l.halo_done).get(), l.comm_stream));
         if (is_state) l.state_pending = true;
     }
     return SVGF_OK;
@@ -429,7 +430,7 @@ int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, b
 
 int wait_exchange(svgf_strips* s, svgf_strips::Local& l, bool is_state) {
     DeviceGuard dg(l.device);
-    SVGF_SHIP(s, hipStreamWaitEvent(l.cur, is_state ? l.state_done : l.halo_done, 0));
+    SVGF_SHIP(s, hipStreamWaitEvent(l.cur, (is_state ? l.state_done : l.halo_done).get(), 0));
     if (is_state) l.state_pending = false;
     return SVGF_OK;
 }
@@ -443,13 +444,13 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src
     DeviceGuard dg(l.device);
     c->rb = rows.a; c->re = rows.b;
     const bool timed = s->timing_every > 0 && ((s->frame_no - s->timing_base) % s->timing_every) == 0 && l.rank == s->local[0].rank;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     if (timed) {
-        SVGF_SHIP(s, hipEventCreate(&e0));
-        if (hipError_t e = hipEventCreate(&e1); e != hipSuccess) { (void)hipEventDestroy(e0); return sfail(s, SVGF_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
-        if (hipError_t e = hipEventRecord(e0, l.cur); e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return sfail(s, SVGF_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e)); }
+        SVGF_SHIP(s, acquire(e0, hipEventCreate));
+        SVGF_SHIP(s, acquire(e1, hipEventCreate));
+        SVGF_SHIP(s, hipEventRecord(e0.get(), l.cur));
     }
-    const void* guide = use_guide(c) ? c->guide : nullptr;
+    const void* guide = use_guide(c) ? c->guide.get() : nullptr;
     int rc = SVGF_OK;
     if (inner) {
         svgf::AtrousRanges r{};
@@ -458,18 +459,15 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src
         r.nfirst = r.n;
         add(inner->a, inner->b);
         const int slot = l.cur == l.compute ? 0 : 1;
-        r.signal = l.edge_signal[slot]; r.arrivals = l.edge_arrivals + 64 * slot; r.value = ++l.edge_value[slot];
-        rc = atrous_ranges_impl(c, c->filter[src], c->filter[dst], i == 0 ? c->colour[P] : nullptr, cur, 1 << i, i, guide, r);
+        r.signal = l.edge_signal[slot].get(); r.arrivals = l.edge_arrivals.get() + 64 * slot; r.value = ++l.edge_value[slot];
+        rc = atrous_ranges_impl(c, c->filter[src].get(), c->filter[dst].get(), i == 0 ? c->colour[P].get() : nullptr, cur, 1 << i, i, guide, r);
         if (rc == SVGF_OK) { l.edge_pending = r.nfirst > 0; l.edge_slot = slot; }
-    } else rc = pair ? atrous_pair_impl(c, c->filter[src], c->filter[dst], c->colour[P], cur, guide)
-                     : atrous_impl(c, c->filter[src], c->filter[dst], i == 0 ? c->colour[P] : nullptr, cur, 1 << i, i, guide);
-    if (rc != SVGF_OK) {
-        if (timed) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-        return sfail(s, rc, c->err);
-    }
+    } else rc = pair ? atrous_pair_impl(c, c->filter[src].get(), c->filter[dst].get(), c->colour[P].get(), cur, guide)
+                     : atrous_impl(c, c->filter[src].get(), c->filter[dst].get(), i == 0 ? c->colour[P].get() : nullptr, cur, 1 << i, i, guide);
+    if (rc != SVGF_OK) return sfail(s, rc, c->err);
     if (timed) {
-        if (hipError_t e = hipEventRecord(e1, l.cur); e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return sfail(s, SVGF_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e)); }
-        l.tev.push_back(e0); l.tev.push_back(e1);
+        SVGF_SHIP(s, hipEventRecord(e1.get(), l.cur));
+        l.tev.push_back(std::move(e0)); l.tev.push_back(std::move(e1));
         // (rows of the interior that were left to the NEXT launch are that launch's: left_out)
         l.tbytes_px.push_back((double)((rows.b - rows.a) - (inner && left_out ? left_out->b - left_out->a : 0)) * s->W);
         l.titer.push_back(pair ? -1 : i);
@@ -602,7 +600,7 @@ int svgf_strips_create(svgf_strips** out, int width, int height, int world, cons
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return SVGF_ERR_NO_DEVICE; }
         for (int k = 0; k < nlocal; k++) if (devices[k] < 0 || devices[k] >= ndev) return SVGF_ERR_NO_DEVICE;
     }
-    std::unique_ptr<svgf_strips> s(new (std::nothrow) svgf_strips());
+    std::unique_ptr<svgf_strips, void (*)(svgf_strips*)> s(new (std::nothrow) svgf_strips(), svgf_strips_destroy);   // (a failure below destroys it)
     if (!s) return SVGF_ERR_ALLOC;
     s->W = width; s->H = height; s->world = world; s->steps = params->steps; s->motion_reach = motion_reach;
     s->moments_radius = params->moments_radius; s->storage = params->storage;
@@ -612,18 +610,17 @@ int svgf_strips_create(svgf_strips** out, int width, int height, int world, cons
     if (rc != SVGF_OK) return rc;
     s->plan = lay.plan;
     s->local.resize(nlocal);
-    auto cleanup = [&]() { svgf_strips* p = s.release(); svgf_strips_destroy(p); };
     for (int k = 0; k < nlocal; k++) {
         auto& l = s->local[k];
         l.rank = ranks[k]; l.device = devices[k];
-        if (l.rank < 0 || l.rank >= world) { cleanup(); return SVGF_ERR_INVALID; }
+        if (l.rank < 0 || l.rank >= world) return SVGF_ERR_INVALID;
         make_geo(width, height, l.rank, world, params->steps, s->plan, params->moments_radius, motion_reach, l.g);
         l.compute = compute_streams ? (hipStream_t)compute_streams[k] : nullptr;
         l.cur = l.compute;
         l.comm = comms && !s->mailbox ? (ncclComm_t)comms[s->loopback ? 0 : k] : nullptr;
         svgf_strip st{l.g.y0, l.g.y1 - l.g.y0, l.g.own0, l.g.own1};
         rc = svgf_create_strip(&l.ctx, width, height, &st, params, l.device, l.compute);
-        if (rc != SVGF_OK) { cleanup(); return rc; }
+        if (rc != SVGF_OK) return rc;
         l.ctx->strip_drv = reinterpret_cast<svgf_strip_driver*>(s.get());
         // previous-frame state is kept up to date own +- halo_state rows (computed here or received); the planes hold more
         // rows (the a-trous halos): the temporal stage must never take state from those
@@ -637,32 +634,33 @@ int svgf_strips_create(svgf_strips** out, int width, int height, int world, cons
             // should long be over (the exchange is then exposed in front of the next iteration)
             int least = 0, greatest = 0;
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            e = hipStreamCreateWithPriority(&l.comm_stream, hipStreamNonBlocking, greatest);
-            l.own_comm_stream = true;
+            e = acquire(l.own_comm, hipStreamCreateWithPriority, hipStreamNonBlocking, greatest);
+            l.comm_stream = l.own_comm.get();
         }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&l.ready, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&l.halo_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&l.state_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = acquire(l.ready, hipEventCreateWithFlags, hipEventDisableTiming);
+        if (e == hipSuccess) e = acquire(l.halo_done, hipEventCreateWithFlags, hipEventDisableTiming);
+        if (e == hipSuccess) e = acquire(l.state_done, hipEventCreateWithFlags, hipEventDisableTiming);
         if (e == hipSuccess && world > 1) {
             int can = 0;
             // (a part or runtime without stream memory operations keeps round 4's three launches per exchanging iteration)
             if (hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, l.device) == hipSuccess && can) {
                 bool sig = true;
                 for (int k = 0; k < 2 && sig; k++) {
-                    sig = hipExtMallocWithFlags((void**)&l.edge_signal[k], 8, hipMallocSignalMemory) == hipSuccess && hipMemset(l.edge_signal[k], 0, 8) == hipSuccess;
+                    auto signal_memory = [](unsigned long long** p) { return hipExtMallocWithFlags((void**)p, 8, hipMallocSignalMemory); };
+                    sig = acquire(l.edge_signal[k], signal_memory) == hipSuccess && hipMemset(l.edge_signal[k].get(), 0, 8) == hipSuccess;
                     if (!sig) (void)hipGetLastError();
                 }
                 if (!sig) {                                    // no signal memory here: the three-launch schedule (edge_signal[0] == null says so)
-                    for (auto& p : l.edge_signal) { if (p) (void)hipFree(p); p = nullptr; }
+                    for (auto& p : l.edge_signal) p.reset();
                 } else {
-                    e = hipMalloc((void**)&l.edge_arrivals, 512);
-                    if (e == hipSuccess) e = hipMemset(l.edge_arrivals, 0, 512);
+                    e = acquire(l.edge_arrivals, hipMalloc<unsigned>, 512);
+                    if (e == hipSuccess) e = hipMemset(l.edge_arrivals.get(), 0, 512);
                 }
             }
         }
-        if (e == hipSuccess && s->mailbox) e = hipEventCreateWithFlags(&l.mb_ready, hipEventDisableTiming);
-        if (e == hipSuccess && s->mailbox) e = hipEventCreateWithFlags(&l.mb_done, hipEventDisableTiming);
-        if (e != hipSuccess) { cleanup(); return SVGF_ERR_HIP; }
+        if (e == hipSuccess && s->mailbox) e = acquire(l.mb_ready, hipEventCreateWithFlags, hipEventDisableTiming);
+        if (e == hipSuccess && s->mailbox) e = acquire(l.mb_done, hipEventCreateWithFlags, hipEventDisableTiming);
+        if (e != hipSuccess) return SVGF_ERR_HIP;
     }
     *out = s.release();
     return SVGF_OK;
@@ -670,25 +668,18 @@ int svgf_strips_create(svgf_strips** out, int width, int height, int world, cons
 
 void svgf_strips_destroy(svgf_strips* s) {
     if (!s) return;
+    // every rank's streams are drained before any rank releases anything: a mailbox copy on one rank's communication stream reads another
+    // rank's planes, and loop-back ranks k > 0 use rank 0's communication stream
     for (auto& l : s->local) {
         DeviceGuard dg(l.device);
         if (l.comm_stream) (void)hipStreamSynchronize(l.comm_stream);
-        if (l.side) (void)hipStreamSynchronize(l.side);
-        if (l.ctx) { (void)hipStreamSynchronize(l.compute); l.ctx->stream = l.compute; l.ctx->strip_drv = nullptr; svgf_destroy(l.ctx); }
-        for (void* p : l.filter_alt) if (p) (void)hipFree(p);
-        if (l.ev_first) (void)hipEventDestroy(l.ev_first);
-        if (l.ev_tail) (void)hipEventDestroy(l.ev_tail);
-        if (l.side) (void)hipStreamDestroy(l.side);
-        for (auto e : l.tev) (void)hipEventDestroy(e);
-        for (auto e : l.frame_done) if (e) (void)hipEventDestroy(e);
-        if (l.ready) (void)hipEventDestroy(l.ready);
-        if (l.halo_done) (void)hipEventDestroy(l.halo_done);
-        if (l.state_done) (void)hipEventDestroy(l.state_done);
-        for (void* p : l.edge_signal) if (p) (void)hipFree(p);
-        if (l.edge_arrivals) (void)hipFree(l.edge_arrivals);
-        if (l.mb_ready) (void)hipEventDestroy(l.mb_ready);
-        if (l.mb_done) (void)hipEventDestroy(l.mb_done);
-        if (l.own_comm_stream && l.comm_stream) (void)hipStreamDestroy(l.comm_stream);
+        if (l.side) (void)hipStreamSynchronize(l.side.get());
+        if (l.ctx) (void)hipStreamSynchronize(l.compute);
+    }
+    for (auto& l : s->local) {
+        DeviceGuard dg(l.device);
+        if (l.ctx) { l.ctx->stream = l.compute; l.ctx->strip_drv = nullptr; svgf_destroy(l.ctx); }
+        l = svgf_strips::Local();                 // (its handles release what it owns, on its device)
     }
     delete s;
 }
@@ -718,9 +709,9 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         DeviceGuard dg(l.device);
         if (!radiance[k]) return sfail(s, SVGF_ERR_INVALID, "svgf_strips_frame: null radiance");
         l.cur = l.compute; c->stream = l.compute;      // (a frame that failed behind its go_aside leaves them on the side stream)
-        if (l.frame_done.empty()) l.frame_done.assign(kMaxAhead, nullptr);
+        if (l.frame_done.empty()) l.frame_done.resize(kMaxAhead);
         // the end of frame f - kMaxAhead (an event record is a barrier packet on the filter stream, ~6 us with nothing running: every kAheadStride-th frame carries one)
-        if (s->frame_no % kAheadStride == 0) if (hipEvent_t old = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)]) SVGF_SHIP(s, hipEventSynchronize(old));
+        if (s->frame_no % kAheadStride == 0) if (hipEvent_t old = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)].get()) SVGF_SHIP(s, hipEventSynchronize(old));
         int rc0 = alloc_state(c);                 // svgf_denoise_frame's lazy allocation (exact size, zeroed)
         if (rc0 == SVGF_OK) rc0 = alloc_flags(c);
         if (rc0 != SVGF_OK) return sfail(s, rc0, c->err);
@@ -730,8 +721,8 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
             // filter stream was made to wait for in the previous call (go_aside).
             for (int i = 0; i < 2; i++) {
                 if (!l.filter_alt[i]) {
-                    SVGF_SHIP(s, hipMalloc(&l.filter_alt[i], colour_bytes(c)));
-                    SVGF_SHIP(s, hipMemsetAsync(l.filter_alt[i], 0, colour_bytes(c), l.compute));
+                    SVGF_SHIP(s, acquire(l.filter_alt[i], hipMalloc<void>, colour_bytes(c)));
+                    SVGF_SHIP(s, hipMemsetAsync(l.filter_alt[i].get(), 0, colour_bytes(c), l.compute));
                 }
                 std::swap(c->filter[i], l.filter_alt[i]);
             }
@@ -749,14 +740,14 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         if (!pv->motion) pv = &cur[k];
         const Rows rt = grown(l.g, s->H, l.g.ext_temporal), rm = grown(l.g, s->H, l.g.ext_moments);
         c->rb = rt.a; c->re = rt.b;
-        void* guide = use_guide(c) ? c->guide : nullptr;      // as svgf_denoise_frame: the temporal launch repacks {depth, ddepth, normal} for the iterations
+        void* guide = use_guide(c) ? c->guide.get() : nullptr;      // as svgf_denoise_frame: the temporal launch repacks {depth, ddepth, normal} for the iterations
         const void* guide_prev = prev_guide_for(c, &cur[k], pv);   // the previous frame's guide plane stands in for its G-buffer (all held rows)
         c->guide_prev_valid = false;                               // until this frame has written its own (commit_guide below)
         // which kernel serves the strip's young pixels (svgf_api.hip: every rank chooses for itself, the results do not depend on it)
         bool cold = false, crowded = false;
         choose_moments_kernel(c, &cold, &crowded);
-        int rc = temporal_moments_impl(c, c->colour[1 - P], radiance[k], c->colour[P], c->filter[0], &cur[k], pv, c->hist[1 - P], c->hist[P],
-                                       c->moments[P], c->moments[1 - P], rm.a, rm.b, s->steps >= 1 && !crowded, guide, guide_prev, cold || crowded);
+        int rc = temporal_moments_impl(c, c->colour[1 - P].get(), radiance[k], c->colour[P].get(), c->filter[0].get(), &cur[k], pv, c->hist[1 - P].get(),
+                                       c->hist[P].get(), c->moments[P].get(), c->moments[1 - P].get(), rm.a, rm.b, s->steps >= 1 && !crowded, guide, guide_prev, cold || crowded);
         // (the temporal launch also writes the guide texels of the rows the strip holds beyond the temporal rows: the a-trous halos
         // of the later iteration groups and the next frame's reprojection read them)
         if (rc != SVGF_OK) return sfail(s, rc, c->err);
@@ -791,13 +782,13 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         for (int k = 0; k < n; k++) {
             auto& l = s->local[k];
             DeviceGuard dg(l.device);
-            SVGF_SHIP(s, hipEventRecord(l.ev_first, l.compute));
+            SVGF_SHIP(s, hipEventRecord(l.ev_first.get(), l.compute));
             // the frame that was on the side stream is ordered on the filter stream first: its result may be consumed after this call, its
             // pair of planes reused by the next one
-            if (l.tail_pending) { SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail, 0)); l.tail_pending = false; }
-            SVGF_SHIP(s, hipStreamWaitEvent(l.side, l.ev_first, 0));
-            l.cur = l.side;
-            l.ctx->stream = l.side;
+            if (l.tail_pending) { SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0)); l.tail_pending = false; }
+            SVGF_SHIP(s, hipStreamWaitEvent(l.side.get(), l.ev_first.get(), 0));
+            l.cur = l.side.get();
+            l.ctx->stream = l.side.get();
         }
         aside = true;
         return SVGF_OK;
@@ -915,22 +906,22 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         {
             DeviceGuard dg(l.device);
             if (s->frame_no % kAheadStride == 0) {
-                hipEvent_t& done = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)];
-                if (!done) SVGF_SHIP(s, hipEventCreateWithFlags(&done, hipEventDisableTiming));
-                SVGF_SHIP(s, hipEventRecord(done, l.cur));
+                Event& done = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)];
+                if (!done) SVGF_SHIP(s, acquire(done, hipEventCreateWithFlags, hipEventDisableTiming));
+                SVGF_SHIP(s, hipEventRecord(done.get(), l.cur));
             }
             if (l.cur != l.compute) {             // the end of this frame's tail on the side stream
-                SVGF_SHIP(s, hipEventRecord(l.ev_tail, l.cur));
+                SVGF_SHIP(s, hipEventRecord(l.ev_tail.get(), l.cur));
                 l.tail_pending = true;
             } else if (l.tail_pending) {          // this frame never left the filter stream: the one in flight is ordered behind it now
-                SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail, 0));
+                SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0));
                 l.tail_pending = false;
             }
             l.cur = l.compute;
             c->stream = l.compute;
         }
         c->rb = c->strip.own_begin; c->re = c->strip.own_end;
-        if (results) results[k] = c->filter[pp[k]];
+        if (results) results[k] = c->filter[pp[k]].get();
         c->result_index = pp[k];
         commit_guide(c, &cur[k], use_guide(c));
         c->pingpong ^= 1;
@@ -952,12 +943,12 @@ int svgf_strips_set_frames_in_flight(svgf_strips* s, int frames) {
             if (!l.side) {                        // at the filter stream's priority (a default-priority stream beside a high-priority one is starved)
                 int prio = 0;
                 (void)hipStreamGetPriority(l.compute, &prio);
-                SVGF_SHIP(s, hipStreamCreateWithPriority(&l.side, hipStreamNonBlocking, prio));
+                SVGF_SHIP(s, acquire(l.side, hipStreamCreateWithPriority, hipStreamNonBlocking, prio));
             }
-            if (!l.ev_first) SVGF_SHIP(s, hipEventCreateWithFlags(&l.ev_first, hipEventDisableTiming));
-            if (!l.ev_tail) SVGF_SHIP(s, hipEventCreateWithFlags(&l.ev_tail, hipEventDisableTiming));
+            if (!l.ev_first) SVGF_SHIP(s, acquire(l.ev_first, hipEventCreateWithFlags, hipEventDisableTiming));
+            if (!l.ev_tail) SVGF_SHIP(s, acquire(l.ev_tail, hipEventCreateWithFlags, hipEventDisableTiming));
         } else if (l.tail_pending) {              // back to one frame at a time: the filter stream waits for the tail in flight
-            SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail, 0));
+            SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0));
             l.tail_pending = false;
         }
     }
@@ -982,9 +973,9 @@ int svgf_strips_sync(svgf_strips* s) {
         unsigned long long n = 0;
         int rc = read_halo_violations(l.ctx, &n, 1);
         if (rc != SVGF_OK) return sfail(s, rc, l.ctx->err);
-        if (l.tail_pending) { SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail, 0)); l.tail_pending = false; }
+        if (l.tail_pending) { SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0)); l.tail_pending = false; }
         SVGF_SHIP(s, hipStreamSynchronize(l.compute));
-        if (l.side) SVGF_SHIP(s, hipStreamSynchronize(l.side));
+        if (l.side) SVGF_SHIP(s, hipStreamSynchronize(l.side.get()));
         SVGF_SHIP(s, hipStreamSynchronize(l.comm_stream));
         total += n;
     }
@@ -1005,16 +996,18 @@ int svgf_strips_timing_read(svgf_strips* s, int* launches, double* ms, double* p
     if (!s || !launches || !ms || !px_all || !px_iter0) return SVGF_ERR_INVALID;
     auto& l = s->local[0];
     DeviceGuard dg(l.device);
-    for (size_t i = 0; i + 1 < l.tev.size(); i += 2) {
-        SVGF_SHIP(s, hipEventSynchronize(l.tev[i + 1]));
+    // the lists are consumed whatever happens below: a failure destroys the events with them and leaves none listed
+    const std::vector<Event> tev = std::move(l.tev);
+    const std::vector<double> tbytes_px = std::move(l.tbytes_px);
+    const std::vector<int> titer = std::move(l.titer);
+    for (size_t i = 0; i + 1 < tev.size(); i += 2) {
+        SVGF_SHIP(s, hipEventSynchronize(tev[i + 1].get()));
         float t = 0.f;
-        SVGF_SHIP(s, hipEventElapsedTime(&t, l.tev[i], l.tev[i + 1]));
+        SVGF_SHIP(s, hipEventElapsedTime(&t, tev[i].get(), tev[i + 1].get()));
         s->t_ms += t; s->t_launches++;
-        s->t_px_iter += l.tbytes_px[i / 2] * (l.titer[i / 2] < 0 ? 2.0 : 1.0);       // a pair launch covers its rows in two iterations
-        if (l.titer[i / 2] <= 0) s->t_px_fb += l.tbytes_px[i / 2];
-        (void)hipEventDestroy(l.tev[i]); (void)hipEventDestroy(l.tev[i + 1]);
+        s->t_px_iter += tbytes_px[i / 2] * (titer[i / 2] < 0 ? 2.0 : 1.0);       // a pair launch covers its rows in two iterations
+        if (titer[i / 2] <= 0) s->t_px_fb += tbytes_px[i / 2];
     }
-    l.tev.clear(); l.tbytes_px.clear(); l.titer.clear();
     *launches = s->t_launches; *ms = s->t_ms; *px_all = s->t_px_iter; *px_iter0 = s->t_px_fb;
     s->t_launches = 0; s->t_ms = 0; s->t_px_iter = 0; s->t_px_fb = 0;
     return SVGF_OK;
