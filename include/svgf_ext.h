@@ -67,10 +67,13 @@ int svgf_set_iteration_fusion(svgf_ctx* ctx, int enable);
  *   - the planes of `cur` are not read after the call's launches on the context's stream: iterations that read them (the direct kernel:
  *     variant DIRECT, PhiNormal == 0, a step beyond 64) keep the frame's tail on the context's stream — such a frame simply does not
  *     overlap with the next one;
- *   - the debug views (svgf_set_debug_mode) and strip-driver contexts do not combine with it (refused).
+ *   - the debug views (svgf_set_debug_mode) do not combine with it (refused); a strip driver's context refuses any change (its driver
+ *     sets it: svgf_strips_set_frames_in_flight);
+ *   - svgf_state_plane(SVGF_PLANE_FILTER, ..) names the pair of filter planes of the last frame enqueued.
  * frames = 1 (default) restores stream order at once: the frame in flight is ordered on the context's stream by that call and its
  * result is then valid until the next svgf_denoise_frame, as ever.  svgf_flush orders the frame in flight on the context's stream
- * without waiting for it; svgf_reset_history / svgf_resize / svgf_destroy wait for or order it themselves. */
+ * without waiting for it; svgf_reset_history / svgf_resize / svgf_destroy wait for or order it themselves.  All of these see a strip
+ * driver's frame in flight on its contexts (svgf_strips_context) too. */
 int svgf_set_frames_in_flight(svgf_ctx* ctx, int frames);
 int svgf_flush(svgf_ctx* ctx);
 /* Stream capture — a host that records its frame into a hipGraph (hipStreamBeginCapture on the context's stream) can record
@@ -134,10 +137,11 @@ int svgf_path_stats_read(svgf_ctx* ctx, unsigned long long* counts, int slots);
 
 /* ---- The strip driver's switches --------------------------------------------------------------------------------------- */
 /* Two frames in flight for the strips — svgf_set_frames_in_flight for the driver's contexts: with frames = 2, iterations 1.. of a frame
- * (their halo exchanges included) run on a stream of the driver's own beside the NEXT frame's temporal launch; results are bit-identical.
+ * (their halo exchanges included) run on a side stream of every rank beside the NEXT frame's temporal launch; results are bit-identical.
  * results[k] of call f is ORDERED on the rank's compute stream only by call f + 1 or svgf_strips_sync — enqueue its consumer after one of
  * those — and stays valid until call f + 2 (frames alternate between two pairs of filter planes); cur[k] is not read after the call has
- * returned (a frame whose iterations would read it — the direct kernel — keeps its tail on the compute stream).  Default 1. */
+ * returned (a frame whose iterations would read it — the direct kernel — keeps its tail on the compute stream).  Default 1.  The contexts
+ * of the driver keep the frame in flight as svgf_set_frames_in_flight does: svgf_flush, svgf_sync and svgf_reset_history on them order it. */
 int svgf_strips_set_frames_in_flight(svgf_strips* s, int frames);
 /* Edge rows first (opt-in, default 0).  The iteration in front of a halo exchange produces the rows its neighbours wait for FIRST.  Default: two edge
  * launches, an event, the exchange, an interior launch — the exchange ordered by the event, inside HIP's memory model.  With enable = 1 that is

@@ -166,16 +166,6 @@ int alloc_state(svgf_ctx* c) {
     return reset_history(c);
 }
 
-// frames_in_flight == 2: the second pair of filter planes (zeroed like the first, so that both pairs read the same after a reset)
-int alloc_alt(svgf_ctx* c) {
-    if (c->frames_in_flight < 2 || (c->filter_alt[0] && c->filter_alt[1])) return SVGF_OK;
-    for (int i = 0; i < 2; i++) {
-        if (!c->filter_alt[i]) SVGF_HIP(c, acquire(c->filter_alt[i], hipMalloc<void>, colour_bytes(c)));
-        SVGF_HIP(c, hipMemsetAsync(c->filter_alt[i].get(), 0, colour_bytes(c), c->stream));
-    }
-    return SVGF_OK;
-}
-
 int join_side(svgf_ctx* c, hipStream_t onto) {
     if (!c->in_flight) return SVGF_OK;
     if (c->in_flight_capture) {
@@ -188,6 +178,62 @@ int join_side(svgf_ctx* c, hipStream_t onto) {
     SVGF_HIP(c, hipStreamWaitEvent(onto, c->ev_done.get(), 0));
     c->in_flight = false;
     c->in_flight_capture = 0;
+    return SVGF_OK;
+}
+
+// (the callers have checked the argument and refused what they refuse)
+int set_frames_in_flight(svgf_ctx* c, int frames, int side_priority) {
+    if (frames == c->frames_in_flight) return SVGF_OK;
+    if (frames == 2) {
+        if (!c->side) SVGF_HIP(c, acquire(c->side, hipStreamCreateWithPriority, hipStreamNonBlocking, side_priority));
+        if (!c->ev_first) SVGF_HIP(c, acquire(c->ev_first, hipEventCreateWithFlags, hipEventDisableTiming));
+        if (!c->ev_done) SVGF_HIP(c, acquire(c->ev_done, hipEventCreateWithFlags, hipEventDisableTiming));
+        c->swap_pairs = false;                      // the first frame writes the pair the last one wrote
+    } else if (int rc = join_side(c, c->stream); rc != SVGF_OK) return rc;
+    c->frames_in_flight = frames;
+    return SVGF_OK;
+}
+
+// Everything the NEXT frame's temporal launch reads is written once iteration 0 has stored the feedback colour: with two frames in flight the
+// remaining iterations may leave the caller's stream — if they read nothing of the caller's: every one of them an LDS launch on the guide plane.
+// An iteration the direct kernel runs (variant DIRECT, PhiNormal == 0, a step beyond 64) reads cur->motion / cur->normal, which nothing orders
+// against the caller's stream once the call has returned.
+bool tail_may_leave(const svgf_ctx* c, int first) {
+    return first < c->p.steps && use_guide(c) && c->p.variant != SVGF_VARIANT_DIRECT && c->p.phi_normal != 0.0f && (1 << (c->p.steps - 1)) <= 64;
+}
+
+// The rest of this frame goes onto the side stream; the frame that was there is ordered on the caller's stream first (its result may be
+// consumed, its planes reused).
+int fork_side(svgf_ctx* c) {
+    hipStream_t const caller = c->stream;
+    SVGF_HIP(c, hipEventRecord(c->ev_first.get(), caller));
+    if (int rc = join_side(c, caller); rc != SVGF_OK) return rc;
+    SVGF_HIP(c, hipStreamWaitEvent(c->side.get(), c->ev_first.get(), 0));
+    c->stream = c->side.get();
+    return SVGF_OK;
+}
+
+// (also after a failed launch: whatever did get onto the side stream must be waited for before its planes are touched again)
+hipError_t join_back(svgf_ctx* c, hipStream_t caller, unsigned long long capture) {
+    const hipError_t e = hipEventRecord(c->ev_done.get(), c->side.get());
+    if (e == hipSuccess) { c->in_flight = true; c->in_flight_capture = capture; }
+    c->stream = caller;
+    return e;
+}
+
+// With two frames in flight a frame takes the pair of filter planes the frame before the last one wrote (whose tail the caller's stream has been
+// made to wait for by the last frame's fork or join): the two pairs swap names, and every helper keeps saying c->filter[].  The second pair
+// is zeroed like the first, so that both pairs read the same after a reset.
+int begin_frame(svgf_ctx* c) {
+    int rc = alloc_state(c);
+    if (rc == SVGF_OK) rc = alloc_flags(c);
+    if (rc != SVGF_OK || c->frames_in_flight < 2) return rc;
+    if (!c->filter_alt[0] || !c->filter_alt[1]) for (int i = 0; i < 2; i++) {
+        if (!c->filter_alt[i]) SVGF_HIP(c, acquire(c->filter_alt[i], hipMalloc<void>, colour_bytes(c)));
+        SVGF_HIP(c, hipMemsetAsync(c->filter_alt[i].get(), 0, colour_bytes(c), c->stream));
+    }
+    if (c->swap_pairs) for (int i = 0; i < 2; i++) std::swap(c->filter[i], c->filter_alt[i]);
+    c->swap_pairs = true;
     return SVGF_OK;
 }
 
@@ -297,11 +343,16 @@ const void* prev_guide_for(const svgf_ctx* c, const svgf_gbuffer* cur, const svg
     return c->guide_prev.get();
 }
 
-void commit_guide(svgf_ctx* c, const svgf_gbuffer* cur, bool written) {
-    if (!written || !cur) { c->guide_prev_valid = false; return; }
-    std::swap(c->guide, c->guide_prev);
-    c->guide_prev_of = *cur;
-    c->guide_prev_valid = true;
+// The end of a frame: the guide just written (the temporal launch covers all held rows) becomes the previous one.
+void finish_frame(svgf_ctx* c, int result_index, const svgf_gbuffer* cur, bool guide_written) {
+    c->result_index = result_index;
+    c->guide_prev_valid = guide_written && cur;
+    if (c->guide_prev_valid) {
+        std::swap(c->guide, c->guide_prev);
+        c->guide_prev_of = *cur;
+    }
+    c->pingpong ^= 1;                               // App.cu:374
+    if (c->frames_since_reset < (1 << 30)) c->frames_since_reset++;
 }
 
 // svgf_path_stats_enable: the counter pair of step 1 << i (the LDS-streaming kernel's steps), or null
@@ -502,7 +553,7 @@ int svgf_resize_strip(svgf_ctx* c, int width, int height, const svgf_strip* stri
     c->have_state = false; c->guide_prev_valid = false;
     c->W = width; c->H = height; c->strip = *strip; c->rb = strip->own_begin; c->re = strip->own_end;
     c->vy0 = strip->y0; c->vy1 = strip->y0 + strip->rows;
-    c->pingpong = 0; c->frames_since_reset = 0; c->result_index = 0; c->filter_set = 0; c->last_pair_alt = false;
+    c->pingpong = 0; c->frames_since_reset = 0; c->result_index = 0; c->swap_pairs = false;
     return SVGF_OK;
 }
 
@@ -631,30 +682,10 @@ int svgf_set_frames_in_flight(svgf_ctx* c, int frames) {
     if (!c) return SVGF_ERR_INVALID;
     if (frames != 1 && frames != 2) return fail(c, SVGF_ERR_INVALID, "svgf_set_frames_in_flight: 1 or 2");
     if (frames == c->frames_in_flight) return SVGF_OK;
-    if (frames == 2 && c->strip_drv) return fail(c, SVGF_ERR_INVALID, "svgf_set_frames_in_flight: the strip driver schedules its contexts itself");
+    if (c->strip_drv) return fail(c, SVGF_ERR_INVALID, "svgf_set_frames_in_flight: the strip driver schedules its contexts itself");
     if (frames == 2 && c->debug_mode != SVGF_DEBUG_FINAL) return fail(c, SVGF_ERR_INVALID, "svgf_set_frames_in_flight: not with a debug view selected");
     DeviceGuard dg(c->device);
-    if (frames == 2) {
-        if (!c->side) SVGF_HIP(c, acquire(c->side, hipStreamCreateWithFlags, hipStreamNonBlocking));
-        if (!c->ev_first) SVGF_HIP(c, acquire(c->ev_first, hipEventCreateWithFlags, hipEventDisableTiming));
-        if (!c->ev_done) SVGF_HIP(c, acquire(c->ev_done, hipEventCreateWithFlags, hipEventDisableTiming));
-    } else {
-        int rc = join_side(c, c->stream);
-        if (rc != SVGF_OK) return rc;
-        // With one frame in flight every frame uses c->filter[], and svgf_state_plane(SVGF_PLANE_FILTER, ..) and the SVGF_DEBUG_ATROUS view
-        // (which filters what the previous frame left in FilterBuffer, App.cu:611-620) index c->filter[] too: if the last frame used the
-        // second pair, the pairs change names (the result pointer handed out stays valid: the planes themselves do not move).
-        // (last_pair_alt is what the last FRAME wrote — not what filter_set implies: 2 -> 1 -> 2 -> 1 without a frame between the last two
-        // switches must not swap again)
-        if (c->last_pair_alt && c->filter_alt[0] && c->filter_alt[1]) {
-            std::swap(c->filter[0], c->filter_alt[0]);
-            std::swap(c->filter[1], c->filter_alt[1]);
-            c->last_pair_alt = false;
-        }
-        c->filter_set = 0;
-    }
-    c->frames_in_flight = frames;
-    return SVGF_OK;
+    return set_frames_in_flight(c, frames, 0);      // (the side stream at the default priority)
 }
 
 int svgf_flush(svgf_ctx* c) {
@@ -763,15 +794,9 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
             return fail(c, SVGF_ERR_INVALID, "svgf_denoise_frame: the context's stream is being captured while a frame enqueued before the capture is still in flight: "
                                              "svgf_flush before hipStreamBeginCapture");
     }
-    rc = alloc_state(c);
-    if (rc == SVGF_OK) rc = alloc_flags(c);
-    if (rc == SVGF_OK) rc = alloc_alt(c);
+    rc = begin_frame(c);                            // (frames in flight: the previous frame's result sits in the other pair until the call after this)
     if (rc != SVGF_OK) return rc;
     const int P = c->pingpong;
-    // frames in flight: this frame's pair of filter planes (the previous frame's result sits in the other one until the call after this)
-    const DevicePtr<void>* const F = c->frames_in_flight > 1 && c->filter_set ? c->filter_alt : c->filter;
-    c->last_pair_alt = F == c->filter_alt;
-    if (c->frames_in_flight > 1) c->filter_set ^= 1;
 
     svgf_ctx::FrameEvents fe;
     const bool timed = !cap && c->timing > 0 && (c->timing_phase++ % c->timing) == 0;     // (events of a captured frame are graph nodes: nothing to read back)
@@ -797,15 +822,14 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         if (rc != SVGF_OK) return bail(rc);
         stamp(); stamp();
         const void* res = c->colour[P].get();
+        int pp = c->result_index;
         if (c->debug_mode == SVGF_DEBUG_ATROUS) {
-            int pp = c->result_index;
             for (int i = 0; i < c->p.steps; i++) {
                 rc = atrous_impl(c, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i);
                 if (rc != SVGF_OK) return bail(rc);
                 stamp();
                 pp ^= 1;
             }
-            c->result_index = pp;
             res = c->filter[pp].get();
         }
         if (timed) {
@@ -813,9 +837,7 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
             if (fe.nstage >= 2) c->pending.push_back(std::move(fe)); else bail(0);
         }
         if (result) *result = res;
-        commit_guide(c, cur, false);
-        c->pingpong ^= 1;
-        if (c->frames_since_reset < (1 << 30)) c->frames_since_reset++;
+        finish_frame(c, pp, cur, false);
         return SVGF_OK;
     }
     // With at least one wavelet iteration the temporal result in colour[P] is dead where iteration 0's feedback will
@@ -834,12 +856,12 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     // G-buffer (prev_guide_for): -16 B/px of the temporal launch's 146
     void* guide = use_guide(c) ? c->guide.get() : nullptr;
     rc = temporal_impl(c, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(),
-                       c->moments[P].get(), c->moments[1 - P].get(), F[0].get(), sparse, guide, prev_guide_for(c, cur, prev));  // App.cu:552
+                       c->moments[P].get(), c->moments[1 - P].get(), c->filter[0].get(), sparse, guide, prev_guide_for(c, cur, prev));  // App.cu:552
     c->dense_now = c->cold_now = false;             // (the stage calls on this context keep their lists)
     if (rc != SVGF_OK) return bail(rc);
     stamp();
     // the first three frames after a reset have history <= 3 everywhere: the LDS-streaming moments kernel
-    rc = moments_impl(c, c->colour[P].get(), F[0].get(), c->moments[P].get(), cur, c->hist[P].get(), 1, cold || crowded, sparse);   // App.cu:554 (current moments: App. B #4)
+    rc = moments_impl(c, c->colour[P].get(), c->filter[0].get(), c->moments[P].get(), cur, c->hist[P].get(), 1, cold || crowded, sparse);   // App.cu:554 (current moments: App. B #4)
     if (rc != SVGF_OK) return bail(rc);
     stamp();
     int pp = 0, first = 0;
@@ -848,50 +870,33 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     // rows lie outside what this frame's temporal launch wrote, and feedback computed from last frame's filter plane would replace
     // colour rows the two-launch sequence leaves alone.  So: only on the whole frame.
     const bool pair = can_fuse01(c) && halo_held(c, 6) && c->rb == 0 && c->re == c->H;
-    bool aside = false;
-    auto go_aside = [&]() -> int {
-        // the rest of this frame goes onto the side stream; the frame that was there is ordered on the caller's stream first (its
-        // result may be consumed, its planes reused)
-        hipError_t e = hipEventRecord(c->ev_first.get(), caller_stream);
-        if (e != hipSuccess) return hip_fail(c, e, "hipEventRecord");
-        int r = join_side(c, caller_stream);
-        if (r != SVGF_OK) return r;
-        e = hipStreamWaitEvent(c->side.get(), c->ev_first.get(), 0);
-        if (e != hipSuccess) return hip_fail(c, e, "hipStreamWaitEvent");
-        c->stream = c->side.get();
-        aside = true;
-        stamp();                                                                // the tail's own start: it may have waited for the frame before it
-        return SVGF_OK;
-    };
     if (pair) {
-        // iterations 0 and 1 as one launch: F[0] -> F[1] (iteration 0's own plane is never written), feedback as ever
-        rc = atrous_pair_impl(c, F[0].get(), F[1].get(), c->colour[P].get(), cur, guide);
+        // iterations 0 and 1 as one launch: c->filter[0] -> c->filter[1] (iteration 0's own plane is never written), feedback as ever
+        rc = atrous_pair_impl(c, c->filter[0].get(), c->filter[1].get(), c->colour[P].get(), cur, guide);
         if (rc == SVGF_OK) { stamp(); stamp(); pp = 1; first = 2; }             // timing slot 2 holds the pair, slot 3 (next to) nothing
     } else if (c->p.steps >= 1) {
-        rc = atrous_impl(c, F[0].get(), F[1].get(), c->colour[P].get(), cur, 1, 0, guide);        // App.cu:497-507, iteration 0: feeds the history back
+        rc = atrous_impl(c, c->filter[0].get(), c->filter[1].get(), c->colour[P].get(), cur, 1, 0, guide);        // App.cu:497-507, iteration 0: feeds the history back
         if (rc == SVGF_OK) { stamp(); pp = 1; first = 1; }
     }
-    // Everything the NEXT frame's temporal launch reads is written now: with two frames in flight the remaining iterations leave the
-    // caller's stream.  (Iteration 0 on the side stream as well - the next temporal launch waiting for an event behind it - measured
-    // 1-2 % slower: beside a queue of nothing but wavelet launches the temporal launch gets too few workgroup slots, profiles/r03_small_experiments.txt.)
-    // The tail may only leave the caller's stream if it reads nothing of the caller's: every remaining iteration an LDS launch on the
-    // guide plane.  An iteration the direct kernel runs (variant DIRECT, PhiNormal == 0, a step beyond 64) reads cur->motion / cur->normal,
-    // which nothing orders against the caller's stream once the call has returned.
-    bool tail_reads_cur = guide == nullptr || c->p.variant == SVGF_VARIANT_DIRECT || c->p.phi_normal == 0.0f;
-    for (int i = first; i < c->p.steps; i++) tail_reads_cur = tail_reads_cur || (1 << i) > 64;
+    // With two frames in flight the remaining iterations leave the caller's stream (tail_may_leave).  (Iteration 0 on the side stream as well -
+    // the next temporal launch waiting for an event behind it - measured 1-2 % slower: beside a queue of nothing but wavelet launches the temporal
+    // launch gets too few workgroup slots, profiles/r03_small_experiments.txt.)
+    bool aside = false;
     if (rc == SVGF_OK && c->frames_in_flight > 1) {
-        if (c->side && first < c->p.steps && !tail_reads_cur) { fe.split = 2 + first; rc = go_aside(); }
-        else rc = join_side(c, caller_stream);
+        if (tail_may_leave(c, first)) {
+            fe.split = 2 + first;
+            rc = fork_side(c);
+            aside = rc == SVGF_OK;
+            if (aside) stamp();                                                 // the tail's own start: it may have waited for the frame before it
+        } else rc = join_side(c, caller_stream);
     }
     for (int i = first; i < c->p.steps && rc == SVGF_OK; i++) {
-        rc = atrous_impl(c, F[pp].get(), F[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i, guide);
+        rc = atrous_impl(c, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i, guide);
         if (rc == SVGF_OK) { stamp(); pp ^= 1; }
     }
     if (aside) {
-        // (also after a failed launch: whatever did get onto the side stream must be waited for before its planes are touched again)
-        hipError_t e = hipEventRecord(c->ev_done.get(), c->side.get());
-        if (e == hipSuccess) { c->in_flight = true; c->in_flight_capture = cap; } else if (rc == SVGF_OK) rc = hip_fail(c, e, "hipEventRecord");
-        c->stream = caller_stream;
+        const hipError_t e = join_back(c, caller_stream, cap);
+        if (e != hipSuccess && rc == SVGF_OK) rc = hip_fail(c, e, "hipEventRecord");
     }
     if (rc != SVGF_OK) return bail(rc);
     if (timed) {
@@ -899,11 +904,8 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         if ((int)fe.ev.size() == fe.nstage + 1 + (aside ? 1 : 0)) c->pending.push_back(std::move(fe));
         else bail(0);
     }
-    if (result) *result = F[pp].get();
-    c->result_index = pp;
-    commit_guide(c, cur, guide != nullptr);
-    c->pingpong ^= 1;                                                           // App.cu:374
-    if (c->frames_since_reset < (1 << 30)) c->frames_since_reset++;
+    if (result) *result = c->filter[pp].get();
+    finish_frame(c, pp, cur, guide != nullptr);
     return SVGF_OK;
 }
 

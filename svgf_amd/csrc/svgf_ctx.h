@@ -63,16 +63,15 @@ struct svgf_ctx {
     bool guide_prev_valid = false;
     bool prev_guide_enabled = SVGF_PREV_GUIDE_DEFAULT != 0;   // svgf_set_prev_guide
     bool fuse01 = SVGF_FUSE01_DEFAULT != 0;   // svgf_set_iteration_fusion: iterations 0 and 1 in one launch (frame / strip drivers)
-    // svgf_set_frames_in_flight(2): the frame driver runs iterations 1.. of a frame on `side` while the NEXT frame's temporal, moments
-    // and first-iteration launches run on `stream` (the HBM-bound launch beside the arithmetic-bound ones).  Frames then alternate
-    // between two pairs of filter planes (the guide planes alternate anyway), and a frame's result is ordered on `stream` by the next
-    // svgf_denoise_frame / svgf_flush / svgf_sync.
+    // svgf_set_frames_in_flight(2) / svgf_strips_set_frames_in_flight(2): the frame and strip drivers run iterations 1.. of a frame on `side`
+    // while the NEXT frame's temporal, moments and first-iteration launches run on `stream` (the HBM-bound launch beside the arithmetic-bound
+    // ones).  Frames then alternate between two pairs of filter planes (the guide planes alternate anyway), and a frame's result is ordered
+    // on `stream` by the next frame / svgf_flush / svgf_sync.
     int frames_in_flight = 1;
     svgf_host::Stream side;
     svgf_host::Event ev_first, ev_done;    // iteration 0 of the frame being enqueued is on `stream`; the last iteration of the frame in flight is on `side`
-    svgf_host::DevicePtr<void> filter_alt[2];
-    int filter_set = 0;                    // which pair the NEXT frame uses (toggles per frame while frames_in_flight == 2)
-    bool last_pair_alt = false;            // the last frame wrote filter_alt[] (under its present name): what svgf_set_frames_in_flight(1) renames
+    svgf_host::DevicePtr<void> filter_alt[2];   // the other pair: `filter` always names the pair the last frame enqueued wrote
+    bool swap_pairs = false;               // frames_in_flight == 2: the next frame takes the other pair (false for the first one after the switch or a resize)
     bool in_flight = false;                // a frame's tail is on `side` and `stream` has not been made to wait for it yet
     unsigned long long in_flight_capture = 0;   // ... and the stream capture that tail was recorded in (0: none; svgf.h, Stream capture)
     svgf_host::DevicePtr<unsigned long long> young_masks;   // scratch, temporal -> moments: per (row, 64-column segment) the lanes whose pixel (history < 4) needs the spatial estimate
@@ -139,10 +138,16 @@ size_t moments_bytes(const svgf_ctx* c);
 size_t hist_bytes(const svgf_ctx* c);
 bool is_strip(const svgf_ctx* c);
 int reset_history(svgf_ctx* c);
-int alloc_state(svgf_ctx* c);
-int alloc_flags(svgf_ctx* c);
 int read_halo_violations(svgf_ctx* c, unsigned long long* count, int clear);
+
+// Two frames in flight, one mechanism for the frame and the strip driver (svgf_api.hip)
+int set_frames_in_flight(svgf_ctx* c, int frames, int side_priority);   // 2: creates the side stream (at that priority) and its events; 1: joins the frame in flight
 int join_side(svgf_ctx* c, hipStream_t onto);   // `onto` waits for the frame in flight on the side stream (frames_in_flight == 2); no-op otherwise
+bool tail_may_leave(const svgf_ctx* c, int first);   // iterations first.. of this frame may run on the side stream
+int fork_side(svgf_ctx* c);             // the launches from here on go to the side stream, behind what c->stream holds and the frame in flight
+hipError_t join_back(svgf_ctx* c, hipStream_t caller, unsigned long long capture);   // ... what went there is the frame in flight; c->stream = caller
+int begin_frame(svgf_ctx* c);           // allocates what a frame needs and picks its pair of filter planes: c->filter
+void finish_frame(svgf_ctx* c, int result_index, const svgf_gbuffer* cur, bool guide_written);   // result, guide and ping-pong move on
 
 // the stages on caller- or driver-owned planes, rows [c->rb, c->re); the device is already current
 int temporal_moments_impl(svgf_ctx* c, const void* prev_colour, const void* radiance, void* colour_out, void* filter_out,
@@ -158,7 +163,6 @@ int atrous_ranges_impl(svgf_ctx* c, const void* in, void* out, void* feedback, c
 int atrous_pair_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, const void* guide = nullptr);
 bool can_fuse01(const svgf_ctx* c);     // the drivers run iterations 0 and 1 as one launch
 const void* prev_guide_for(const svgf_ctx* c, const svgf_gbuffer* cur, const svgf_gbuffer* prev);   // the guide plane that stands in for `prev`, or null
-void commit_guide(svgf_ctx* c, const svgf_gbuffer* cur, bool written);   // end of a frame: the guide just written (the temporal launch covers all held rows) becomes the previous one
 bool use_guide(const svgf_ctx* c);      // the frame / strip drivers repack {depth, ddepth, normal, instance ID} for the iterations (any storage, >= 1 iteration, LDS kernels)
 
 }  // namespace svgf_host

@@ -118,13 +118,8 @@ struct svgf_strips {
         ncclComm_t comm = nullptr;
         hipStream_t compute = nullptr, comm_stream = nullptr;   // comm_stream: own_comm, or (loop-back ranks k > 0) rank 0's
         Stream own_comm;
-        // svgf_strips_set_frames_in_flight(2): iterations 1.. of a frame run on `side` beside the next frame's temporal launch; `cur` is the stream
-        // the launches, the exchanges' ready records and their waits go to at the moment (compute, or side for a frame's tail)
-        Stream side;
-        hipStream_t cur = nullptr;
-        Event ev_first, ev_tail;                              // iteration 0 of the frame being enqueued is on `compute`; the end of the tail in flight on `side`
-        bool tail_pending = false;                            // ... which `compute` has not been made to wait for yet
-        DevicePtr<void> filter_alt[2];
+        // svgf_strips_set_frames_in_flight(2): iterations 1.. of a frame run on the context's side stream beside the next frame's temporal launch
+        // (svgf_ctx).  The launches, the exchanges' ready records and their waits go to ctx->stream: `compute`, or the side stream for a frame's tail.
         Event ready, halo_done, state_done;
         Event mb_ready, mb_done;                               // mailbox: this rank's communication stream has reached the group / has received what the group sends it
         // edge rows first (svgf_strips_set_edge_first): the iteration in front of an exchange is ONE launch whose first workgroups produce the rows the
@@ -374,7 +369,7 @@ int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, b
     // profiles/r05_strip_trace_*.txt: it is only recorded where something will wait for it.)
     for (auto& l : s->local) {
         DeviceGuard dg(l.device);
-        if (!in_order && !l.edge_pending) SVGF_SHIP(s, hipEventRecord(l.ready.get(), l.cur));
+        if (!in_order && !l.edge_pending) SVGF_SHIP(s, hipEventRecord(l.ready.get(), l.ctx->stream));
     }
     // (edge rows first: the rows a rank sends are final when the first workgroups of the launch it has just enqueued have signalled — the
     // communication stream waits for that word, not for the launch; everything enqueued BEFORE that launch is complete by then, stream order)
@@ -430,7 +425,7 @@ int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, b
 
 int wait_exchange(svgf_strips* s, svgf_strips::Local& l, bool is_state) {
     DeviceGuard dg(l.device);
-    SVGF_SHIP(s, hipStreamWaitEvent(l.cur, (is_state ? l.state_done : l.halo_done).get(), 0));
+    SVGF_SHIP(s, hipStreamWaitEvent(l.ctx->stream, (is_state ? l.state_done : l.halo_done).get(), 0));
     if (is_state) l.state_pending = false;
     return SVGF_OK;
 }
@@ -448,7 +443,7 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src
     if (timed) {
         SVGF_SHIP(s, acquire(e0, hipEventCreate));
         SVGF_SHIP(s, acquire(e1, hipEventCreate));
-        SVGF_SHIP(s, hipEventRecord(e0.get(), l.cur));
+        SVGF_SHIP(s, hipEventRecord(e0.get(), c->stream));
     }
     const void* guide = use_guide(c) ? c->guide.get() : nullptr;
     int rc = SVGF_OK;
@@ -458,7 +453,7 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src
         add(rows.a, inner->a); add(left_out ? left_out->b : inner->b, rows.b);        // (left_out: interior rows [inner->b, left_out->b) go into the NEXT launch)
         r.nfirst = r.n;
         add(inner->a, inner->b);
-        const int slot = l.cur == l.compute ? 0 : 1;
+        const int slot = c->stream == l.compute ? 0 : 1;
         r.signal = l.edge_signal[slot].get(); r.arrivals = l.edge_arrivals.get() + 64 * slot; r.value = ++l.edge_value[slot];
         rc = atrous_ranges_impl(c, c->filter[src].get(), c->filter[dst].get(), i == 0 ? c->colour[P].get() : nullptr, cur, 1 << i, i, guide, r);
         if (rc == SVGF_OK) { l.edge_pending = r.nfirst > 0; l.edge_slot = slot; }
@@ -466,7 +461,7 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src
                      : atrous_impl(c, c->filter[src].get(), c->filter[dst].get(), i == 0 ? c->colour[P].get() : nullptr, cur, 1 << i, i, guide);
     if (rc != SVGF_OK) return sfail(s, rc, c->err);
     if (timed) {
-        SVGF_SHIP(s, hipEventRecord(e1.get(), l.cur));
+        SVGF_SHIP(s, hipEventRecord(e1.get(), c->stream));
         l.tev.push_back(std::move(e0)); l.tev.push_back(std::move(e1));
         // (rows of the interior that were left to the NEXT launch are that launch's: left_out)
         l.tbytes_px.push_back((double)((rows.b - rows.a) - (inner && left_out ? left_out->b - left_out->a : 0)) * s->W);
@@ -616,7 +611,6 @@ int svgf_strips_create(svgf_strips** out, int width, int height, int world, cons
         if (l.rank < 0 || l.rank >= world) return SVGF_ERR_INVALID;
         make_geo(width, height, l.rank, world, params->steps, s->plan, params->moments_radius, motion_reach, l.g);
         l.compute = compute_streams ? (hipStream_t)compute_streams[k] : nullptr;
-        l.cur = l.compute;
         l.comm = comms && !s->mailbox ? (ncclComm_t)comms[s->loopback ? 0 : k] : nullptr;
         svgf_strip st{l.g.y0, l.g.y1 - l.g.y0, l.g.own0, l.g.own1};
         rc = svgf_create_strip(&l.ctx, width, height, &st, params, l.device, l.compute);
@@ -673,7 +667,7 @@ void svgf_strips_destroy(svgf_strips* s) {
     for (auto& l : s->local) {
         DeviceGuard dg(l.device);
         if (l.comm_stream) (void)hipStreamSynchronize(l.comm_stream);
-        if (l.side) (void)hipStreamSynchronize(l.side.get());
+        if (l.ctx && l.ctx->side) (void)hipStreamSynchronize(l.ctx->side.get());
         if (l.ctx) (void)hipStreamSynchronize(l.compute);
     }
     for (auto& l : s->local) {
@@ -708,25 +702,12 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         svgf_ctx* c = l.ctx;
         DeviceGuard dg(l.device);
         if (!radiance[k]) return sfail(s, SVGF_ERR_INVALID, "svgf_strips_frame: null radiance");
-        l.cur = l.compute; c->stream = l.compute;      // (a frame that failed behind its go_aside leaves them on the side stream)
+        c->stream = l.compute;                    // (a frame that failed behind its fork_side leaves it on the side stream)
         if (l.frame_done.empty()) l.frame_done.resize(kMaxAhead);
         // the end of frame f - kMaxAhead (an event record is a barrier packet on the filter stream, ~6 us with nothing running: every kAheadStride-th frame carries one)
         if (s->frame_no % kAheadStride == 0) if (hipEvent_t old = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)].get()) SVGF_SHIP(s, hipEventSynchronize(old));
-        int rc0 = alloc_state(c);                 // svgf_denoise_frame's lazy allocation (exact size, zeroed)
-        if (rc0 == SVGF_OK) rc0 = alloc_flags(c);
-        if (rc0 != SVGF_OK) return sfail(s, rc0, c->err);
-        if (s->frames_in_flight > 1) {
-            // Two frames in flight: frames alternate between two pairs of filter planes (the context's pointers are swapped, so that every helper
-            // keeps saying c->filter[]); the pair this frame takes over was last used by the frame before the previous one, whose tail the
-            // filter stream was made to wait for in the previous call (go_aside).
-            for (int i = 0; i < 2; i++) {
-                if (!l.filter_alt[i]) {
-                    SVGF_SHIP(s, acquire(l.filter_alt[i], hipMalloc<void>, colour_bytes(c)));
-                    SVGF_SHIP(s, hipMemsetAsync(l.filter_alt[i].get(), 0, colour_bytes(c), l.compute));
-                }
-                std::swap(c->filter[i], l.filter_alt[i]);
-            }
-        }
+        // svgf_denoise_frame's lazy allocation (exact size, zeroed) and, two frames in flight, this frame's pair of filter planes
+        if (int rc = begin_frame(c); rc != SVGF_OK) return sfail(s, rc, c->err);
         // previous-frame state halo: posted by the PREVIOUS frame right after its iteration 0
         if (l.state_pending) { int rc = wait_exchange(s, l, true); if (rc != SVGF_OK) return rc; }
     }
@@ -742,7 +723,7 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         c->rb = rt.a; c->re = rt.b;
         void* guide = use_guide(c) ? c->guide.get() : nullptr;      // as svgf_denoise_frame: the temporal launch repacks {depth, ddepth, normal} for the iterations
         const void* guide_prev = prev_guide_for(c, &cur[k], pv);   // the previous frame's guide plane stands in for its G-buffer (all held rows)
-        c->guide_prev_valid = false;                               // until this frame has written its own (commit_guide below)
+        c->guide_prev_valid = false;                               // until this frame has written its own (finish_frame below)
         // which kernel serves the strip's young pixels (svgf_api.hip: every rank chooses for itself, the results do not depend on it)
         bool cold = false, crowded = false;
         choose_moments_kernel(c, &cold, &crowded);
@@ -768,29 +749,17 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         const int P = s->local[0].ctx->pingpong;           // all local contexts advance together
         return post_exchange(s, state_planes(g, s->steps, P), g.halo_state, true, in_order);
     };
-    // Two frames in flight: everything the NEXT frame's temporal launch reads is written once iteration 0 has stored the feedback colour and
-    // the state exchange is posted; the remaining iterations (their exchanges included) go to the side stream.  Only when they read nothing
-    // of the caller's: LDS launches on the guide plane (the direct kernel reads cur[k], which the caller may rewrite after this call).
-    bool tail_ok = s->frames_in_flight > 1 && s->steps > 1;
-    for (int k = 0; k < n && tail_ok; k++) {
-        const svgf_ctx* c = s->local[k].ctx;
-        tail_ok = use_guide(c) && c->p.variant != SVGF_VARIANT_DIRECT && c->p.phi_normal != 0.0f && (1 << (s->steps - 1)) <= 64;
-    }
+    // Two frames in flight: once iteration 0 has stored the feedback colour and the state exchange is posted, iterations 1.. (their exchanges
+    // included) go to the side stream of every rank, if they may (tail_may_leave) — the frame that was there is ordered on the filter stream first.
+    bool tail_ok = s->frames_in_flight > 1;
+    for (int k = 0; k < n && tail_ok; k++) tail_ok = tail_may_leave(s->local[k].ctx, 1);
     bool aside = false;
-    auto go_aside = [&]() -> int {
-        if (!tail_ok || aside) return SVGF_OK;
-        for (int k = 0; k < n; k++) {
-            auto& l = s->local[k];
-            DeviceGuard dg(l.device);
-            SVGF_SHIP(s, hipEventRecord(l.ev_first.get(), l.compute));
-            // the frame that was on the side stream is ordered on the filter stream first: its result may be consumed after this call, its
-            // pair of planes reused by the next one
-            if (l.tail_pending) { SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0)); l.tail_pending = false; }
-            SVGF_SHIP(s, hipStreamWaitEvent(l.side.get(), l.ev_first.get(), 0));
-            l.cur = l.side.get();
-            l.ctx->stream = l.side.get();
+    auto fork_every_rank = [&]() -> int {
+        for (int k = 0; k < n && tail_ok; k++) {
+            DeviceGuard dg(s->local[k].device);
+            if (int rc = fork_side(s->local[k].ctx); rc != SVGF_OK) return sfail(s, rc, s->local[k].ctx->err);
         }
-        aside = true;
+        aside = tail_ok;
         return SVGF_OK;
     };
     const auto& groups = s->local[0].g.groups;
@@ -818,7 +787,7 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
                     pp[k] ^= 1;
                 }
                 int rc = last_feed < 1 ? post_state(false) : SVGF_OK;
-                if (rc == SVGF_OK) rc = go_aside();
+                if (rc == SVGF_OK) rc = fork_every_rank();
                 if (rc != SVGF_OK) return rc;
                 q++;
                 if (q + 1 == groups[gi].size() && gi + 1 < groups.size() && s->world > 1) {      // (a group of exactly {0, 1}: its output travels whole)
@@ -894,7 +863,7 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
             for (int k = 0; k < n; k++) pp[k] ^= 1;
             if (i == 0) {                             // this frame's state is final once iteration 0 has written the feedback colour
                 int rc = last_feed < 1 ? post_state(false) : SVGF_OK;
-                if (rc == SVGF_OK) rc = go_aside();
+                if (rc == SVGF_OK) rc = fork_every_rank();
                 if (rc != SVGF_OK) return rc;
             }
         }
@@ -903,29 +872,17 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
     for (int k = 0; k < n; k++) {
         auto& l = s->local[k];
         svgf_ctx* c = l.ctx;
-        {
-            DeviceGuard dg(l.device);
-            if (s->frame_no % kAheadStride == 0) {
-                Event& done = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)];
-                if (!done) SVGF_SHIP(s, acquire(done, hipEventCreateWithFlags, hipEventDisableTiming));
-                SVGF_SHIP(s, hipEventRecord(done.get(), l.cur));
-            }
-            if (l.cur != l.compute) {             // the end of this frame's tail on the side stream
-                SVGF_SHIP(s, hipEventRecord(l.ev_tail.get(), l.cur));
-                l.tail_pending = true;
-            } else if (l.tail_pending) {          // this frame never left the filter stream: the one in flight is ordered behind it now
-                SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0));
-                l.tail_pending = false;
-            }
-            l.cur = l.compute;
-            c->stream = l.compute;
+        DeviceGuard dg(l.device);
+        if (s->frame_no % kAheadStride == 0) {
+            Event& done = l.frame_done[(s->frame_no / kAheadStride) % (kMaxAhead / kAheadStride)];
+            if (!done) SVGF_SHIP(s, acquire(done, hipEventCreateWithFlags, hipEventDisableTiming));
+            SVGF_SHIP(s, hipEventRecord(done.get(), c->stream));
         }
+        if (aside) SVGF_SHIP(s, join_back(c, l.compute, 0));       // this frame's tail is the frame in flight now
+        else if (int rc = join_side(c, l.compute); rc != SVGF_OK) return sfail(s, rc, c->err);   // this frame never left the filter stream: the one in flight is ordered behind it
         c->rb = c->strip.own_begin; c->re = c->strip.own_end;
         if (results) results[k] = c->filter[pp[k]].get();
-        c->result_index = pp[k];
-        commit_guide(c, &cur[k], use_guide(c));
-        c->pingpong ^= 1;
-        if (c->frames_since_reset < (1 << 30)) c->frames_since_reset++;
+        finish_frame(c, pp[k], &cur[k], use_guide(c));
     }
     s->frame_no++;
     return SVGF_OK;
@@ -939,18 +896,9 @@ int svgf_strips_set_frames_in_flight(svgf_strips* s, int frames) {
     if (frames == s->frames_in_flight) return SVGF_OK;
     for (auto& l : s->local) {
         DeviceGuard dg(l.device);
-        if (frames == 2) {
-            if (!l.side) {                        // at the filter stream's priority (a default-priority stream beside a high-priority one is starved)
-                int prio = 0;
-                (void)hipStreamGetPriority(l.compute, &prio);
-                SVGF_SHIP(s, acquire(l.side, hipStreamCreateWithPriority, hipStreamNonBlocking, prio));
-            }
-            if (!l.ev_first) SVGF_SHIP(s, acquire(l.ev_first, hipEventCreateWithFlags, hipEventDisableTiming));
-            if (!l.ev_tail) SVGF_SHIP(s, acquire(l.ev_tail, hipEventCreateWithFlags, hipEventDisableTiming));
-        } else if (l.tail_pending) {              // back to one frame at a time: the filter stream waits for the tail in flight
-            SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0));
-            l.tail_pending = false;
-        }
+        int prio = 0;                             // the side stream at the filter stream's priority (a default-priority stream beside a high-priority one is starved)
+        (void)hipStreamGetPriority(l.compute, &prio);
+        if (int rc = set_frames_in_flight(l.ctx, frames, prio); rc != SVGF_OK) return sfail(s, rc, l.ctx->err);
     }
     s->frames_in_flight = frames;
     return SVGF_OK;
@@ -972,10 +920,10 @@ int svgf_strips_sync(svgf_strips* s) {
         DeviceGuard dg(l.device);
         unsigned long long n = 0;
         int rc = read_halo_violations(l.ctx, &n, 1);
+        if (rc == SVGF_OK) rc = join_side(l.ctx, l.compute);
         if (rc != SVGF_OK) return sfail(s, rc, l.ctx->err);
-        if (l.tail_pending) { SVGF_SHIP(s, hipStreamWaitEvent(l.compute, l.ev_tail.get(), 0)); l.tail_pending = false; }
         SVGF_SHIP(s, hipStreamSynchronize(l.compute));
-        if (l.side) SVGF_SHIP(s, hipStreamSynchronize(l.side.get()));
+        if (l.ctx->side) SVGF_SHIP(s, hipStreamSynchronize(l.ctx->side.get()));
         SVGF_SHIP(s, hipStreamSynchronize(l.comm_stream));
         total += n;
     }

@@ -196,6 +196,45 @@ def test_two_frames_in_flight_with_real_peer_addressing(G):
     drv.close()
 
 
+def test_context_calls_order_a_strip_frame_in_flight(G):
+    """Under svgf_strips_set_frames_in_flight(2) a strip's tail is its context's frame in flight: svgf_flush / svgf_sync on a context from
+    svgf_strips_context order it on the rank's compute stream, so frame k may be read there right after them, before call k + 1.  The
+    context refuses a change of frames in flight and a debug view, with the texts of svgf_set_frames_in_flight / svgf_set_debug_mode."""
+    import torch
+    from svgf_amd import filter as F
+    from svgf_amd import strips
+    W, H, world, N, storage = 320, 420, 3, 5, "f32"
+    fr = frames(W, H, N, mv=(1.0, -2.5))
+    whole = G.HipPipeline(W, H, storage, steps=5)
+    side = [torch.cuda.Stream(priority=-1) for _ in range(world)]
+    drv = strips.NativeStrips(W, H, world, F.Params(storage=storage, steps=5), list(range(world)), [0] * world, streams=[s.cuda_stream for s in side],
+                              plan="per-iteration", motion_reach=3, transport="mailbox")
+    drv.set_frames_in_flight(2)
+    lib = drv.lib
+    ctx = [lib.svgf_strips_context(drv._h, r) for r in range(world)]
+    gbs = [G.gb_dev(f) for f in fr]
+    inputs = [[_strip_inputs(G, fr[k], lay, storage) for lay in drv.layouts] for k in range(N)]
+    torch.cuda.synchronize()
+    for k in range(N):
+        want = whole.frame(fr[k]["radiance"], gbs[k], gbs[max(k - 1, 0)])
+        torch.cuda.synchronize()
+        outs = drv.frame([c[0] for c in inputs[k]], [c[1] for c in inputs[k]], [p[1] for p in inputs[k - 1]] if k else None)
+        got = []
+        for r in range(world):
+            assert (lib.svgf_flush if k % 2 == 0 else lib.svgf_sync)(ctx[r]) == 0, lib.svgf_last_error(ctx[r]).decode()
+            with torch.cuda.stream(side[r]):
+                got.append(drv.owned(r, outs[r]).clone())
+        torch.cuda.synchronize()
+        g = np.concatenate([G.host(t) for t in got], 0)
+        assert np.array_equal(g.view(np.uint8), want.view(np.uint8)), f"frame {k}"
+    for r in range(world):
+        assert lib.svgf_set_frames_in_flight(ctx[r], 1) == -1 and b"schedules its contexts itself" in lib.svgf_last_error(ctx[r])
+        assert lib.svgf_set_debug_mode(ctx[r], F.DEBUG_MODE["atrous"]) == -1 and b"frames in flight back to 1" in lib.svgf_last_error(ctx[r])
+        assert lib.svgf_set_frames_in_flight(ctx[r], 2) == 0                      # (no change)
+    drv.sync()
+    drv.close()
+
+
 @pytest.mark.parametrize("fault,text", [(1, "waits for"), (2, "posts no receive"), (3, "expects")])
 def test_the_mailbox_refuses_what_would_deadlock_a_real_run(G, fault, text):
     """The matching itself: drop one send / one receive of rank 1, or post one of its receives with half the size.  On a node the frame would
