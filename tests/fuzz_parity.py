@@ -1,6 +1,7 @@
 """Seeded random sweep of the parity and bit-identity claims (test infrastructure: it calls the oracle; nothing in the product imports it).
 
     python -m tests.fuzz_parity --minutes 10 --seed 1000 [--kinds stage,strips,driver,rows,pair,post,stage0,negzero,strips2,driver2,wide,widestrips,edge,edgedriver,edgestrips,graph,fullsize] [--out gpurun_out/fuzz.txt]
+    python -m tests.fuzz_parity --minutes 30 --seed 1300000 --kinds bigstage          (not in the default list: it would move the kind a seed maps to)
 
 Each trial draws a frame size (down to 1 x 1, up past the 128-pixel tile and the 64-lane wave in both directions), a storage format, the
 tunables over the GUI's ranges (GUI.cpp:988-993), a camera motion, optionally NaN / inf radiance texels and poisoned G-buffer texels
@@ -26,6 +27,8 @@ tunables over the GUI's ranges (GUI.cpp:988-993), a camera motion, optionally Na
   edgedriver, edgestrips   `driver` and `strips` with those tunables, a moments radius of 0-3 and 0-10 (0-7) iterations;
   graph    the frame driver recorded into a HIP graph and replayed against the directly enqueued frames, bit for bit;
   fullsize   1920x1080 and 3840x2160: strip driver and frame driver under a setting against the plain frame driver, bit for bit, poisoned frames;
+  bigstage   one a-trous stage call against the ORACLE at 1920x1080 .. 7680x4320, where the streaming kernel cuts bands longer than its 8-row
+           floor (tests/launch_geometry.py): storage, step, tunables, scene (planar / curved), NaN / inf texels and -0.0 blocks drawn at random;
   stage0   `stage` with -0.0, denormals and the storage type's extremes in the colour and moments planes;
   negzero  `stage0` with rectangles of -0.0 (inside, across the border, over the whole frame) and a tenth of all texels -0.0 in one channel;
   post     the stages after the path: TAA + sRGB against the oracle and tiled against per-pixel, albedo (de)modulation bit-exact.
@@ -45,7 +48,8 @@ from svgf_amd import synth
 from tests.gbuffer_poison import poison_gbuffer
 from tests.helpers import CDT, gbuf
 
-KINDS = ("stage", "strips", "driver", "rows", "pair", "post", "stage0", "negzero", "strips2", "driver2", "wide", "widestrips", "edge", "edgedriver", "edgestrips", "graph", "fullsize")
+KINDS = ("stage", "strips", "driver", "rows", "pair", "post", "stage0", "negzero", "strips2", "driver2", "wide", "widestrips", "edge", "edgedriver", "edgestrips", "graph", "fullsize", "bigstage")
+DEFAULT_KINDS = KINDS[:-1]        # (bigstage runs only when asked for: with it the default list would map every CLI seed to another kind)
 
 
 def _size(rng):
@@ -752,8 +756,9 @@ _FULL = {}
 
 def trial_fullsize(G, oracle, seed):
     """BASELINE.json's frame sizes themselves (1920x1080, 3840x2160): the strip driver (mailbox, world 2-8, any plan) and the frame driver under a
-    random setting against the plain frame driver, bit for bit, on poisoned frames; the history against the oracle's would need minutes of CPU
-    per trial and is left to tests/test_gpu_round2.py's full-size cases.  (The frames of a size are made once per process: synth needs seconds.)"""
+    random setting against the plain frame driver, bit for bit, on poisoned frames.  The stages against the oracle at these sizes are kind
+    `bigstage` and tests/test_gpu_fullsize_parity.py (which also ties the frame driver to the stage calls at 4K under a pan); the history is
+    left to tests/test_gpu_round2.py's full-size cases.  (The frames of a size are made once per process: synth needs seconds.)"""
     import torch
     from svgf_amd import filter as F
     from svgf_amd import strips
@@ -815,7 +820,71 @@ def trial_fullsize(G, oracle, seed):
     return desc
 
 
-TRIALS = {"fullsize": trial_fullsize, "graph": trial_graph, "edgestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, edge=True), "edgedriver": lambda G, oracle, seed: trial_driver(G, oracle, seed, edge=True), "edge": lambda G, oracle, seed: trial_stage(G, oracle, seed, edge=True), "wide": lambda G, oracle, seed: trial_stage(G, oracle, seed, wide=True), "widestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, wide=True),
+_BIG = {}
+BIG_SIZES = [(1920, 1080), (3840, 2160), (4096, 2160), (5120, 2880), (7680, 4320)]
+
+
+def trial_bigstage(G, oracle, seed):
+    """One a-trous stage call (iteration 0, with the feedback plane) against the oracle at a frame size where atrous_lds_kernel cuts long bands:
+    the ring over many steps, the exact re-run of a band that holds a NaN or a -0.0 texel over more than eight rows, the partial last band."""
+    import os
+
+    import torch
+
+    from svgf_amd import filter as F
+    from tests import launch_geometry
+    rng = np.random.default_rng(seed)
+    W, H = BIG_SIZES[int(rng.integers(0, len(BIG_SIZES)))]
+    storage = ("f32", "f16")[int(rng.integers(0, 2))]
+    dt = CDT[storage]
+    step = int(2 ** rng.integers(0, 7))
+    tun = _tunables(rng)
+    scene = ("planar", "curved")[int(rng.integers(0, 2))]
+    k = int(rng.integers(0, 2))
+    nan_texels = int(rng.choice([0, 0, 4, 40]))
+    negzero = int(rng.integers(0, 3))                      # 0: none, 1: rectangles only, 2: rectangles + a tenth of the texels (every band re-runs)
+    nt = min(16, int(os.environ.get("OMP_NUM_THREADS") or 8))
+    geo = launch_geometry.atrous_lds(W, H, step, torch.cuda.get_device_properties(0).multi_processor_count)
+    desc = (f"bigstage seed {seed}: {W}x{H} {storage} step {step} (bands {geo['band']}, last {geo['last_band']}, xgroup {geo['xgroup']}, "
+            f"padding {geo['padding']}) {scene} frame {k} nan {nan_texels} negzero {negzero} phi {tun['phi_colour']:.3g}/{tun['phi_normal']:.3g}")
+    key = (W, H, scene, k)
+    if key not in _BIG:
+        while len(_BIG) >= 2:                              # (a few frames in memory: an 8K one is 2 GB)
+            del _BIG[next(iter(_BIG))]
+        _BIG[key] = synth.make_frame(W, H, k, scene=scene)
+    fs = _BIG[key]
+    src = np.concatenate([fs["radiance"][..., :3] * 1.2 - 0.05, rng.uniform(-0.01, 0.2, (H, W, 1)).astype(np.float32)], -1).astype(dt)
+    if nan_texels:
+        _sprinkle(rng, src, nan_texels)
+    if negzero == 2:
+        _blocks_of_negzero(rng, src, 3)
+    elif negzero == 1:                                     # small rectangles only: some bands re-run, their neighbours do not
+        for _ in range(3):
+            h, w = int(rng.integers(1, 64)), int(rng.integers(1, 256))
+            y, x = int(rng.integers(-h // 2, H)), int(rng.integers(-w // 2, W))
+            src[max(y, 0):y + h, max(x, 0):x + w, np.nonzero(rng.integers(0, 2, 4))[0].tolist() or [0]] = -0.0
+    want = np.zeros_like(src); fbw = np.full_like(src, 7)
+    oracle.atrous(W, H, storage, src, want, fbw, gbuf(fs), step=step, phi_colour=tun["phi_colour"], phi_normal=tun["phi_normal"], iteration=0, nthreads=nt)
+    d = F.Denoiser(W, H, F.Params(storage=storage, variant="auto", **tun))
+    out, fb = d.new_colour(), G.dev(np.full_like(src, 7))
+    d.FilterKernel(G.dev(src), out, fb, G.gb_dev(fs), step, 0)
+    got, got_fb = G.host(out), G.host(fb)
+    d.close()
+    try:
+        _close(G, got, want, storage, desc + ": a-trous")
+        _close(G, got_fb, fbw, storage, desc + ": a-trous feedback")
+        skym = _sky_mask(fs)
+        assert _same_bits(got[skym], want[skym]), desc + ": a-trous sky copy"
+        assert _same_bits(got_fb[skym], fbw[skym]), desc + ": a-trous feedback on sky"
+        zero = (want == 0) & (got == 0)
+        assert np.array_equal(np.signbit(got[zero]), np.signbit(want[zero])), desc + ": a-trous sign of zero"
+    except AssertionError as e:
+        bad = np.argwhere(np.isnan(got.astype(np.float32)) != np.isnan(want.astype(np.float32)))[:4].tolist()
+        raise AssertionError(f"{e} (first NaN-mask differences at {bad}; step {step} rows per band {geo['band']})") from e
+    return desc
+
+
+TRIALS = {"bigstage": trial_bigstage, "fullsize": trial_fullsize, "graph": trial_graph, "edgestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, edge=True), "edgedriver": lambda G, oracle, seed: trial_driver(G, oracle, seed, edge=True), "edge": lambda G, oracle, seed: trial_stage(G, oracle, seed, edge=True), "wide": lambda G, oracle, seed: trial_stage(G, oracle, seed, wide=True), "widestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, wide=True),
           "driver2": trial_driver2, "strips2": trial_strips2, "stage0": lambda G, oracle, seed: trial_stage(G, oracle, seed, zeros=True), "negzero": lambda G, oracle, seed: trial_stage(G, oracle, seed, zeros=2), "stage": trial_stage, "strips": trial_strips, "driver": trial_driver, "rows": trial_rows, "pair": trial_pair, "post": trial_post}
 
 
@@ -831,7 +900,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minutes", type=float, default=5.0)
     ap.add_argument("--seed", type=int, default=1000)
-    ap.add_argument("--kinds", default=",".join(KINDS))
+    ap.add_argument("--kinds", default=",".join(DEFAULT_KINDS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch

@@ -26,7 +26,7 @@ def host(t):
 #   fp16 storage: every stage re-quantises to 11-bit significands; a result within rounding distance of a
 #   half boundary may flip by one half-ulp.
 TOL = {
-    "f32": dict(colour_abs=2e-5, colour_rel=1e-5, var_abs=2e-6, var_rel=2e-4),
+    "f32": dict(colour_abs=2e-5, colour_rel=1e-5, var_abs=2e-6, var_rel=1e-4),
     "f16": dict(max_ulp=1, frac=2e-3),
 }
 

@@ -510,8 +510,8 @@ def test_abi_errors(G):
 # ------------------------------------------------------------------ full-size properties ------
 @pytest.mark.parametrize("storage", ["f32", "f16"])
 def test_4k_properties(G, storage):
-    """At BASELINE's 3840x2160 the oracle is too slow; check size-independent properties instead:
-    (1) all-sky frame -> clamped copy; (2) uniform colour on a flat surface is a fixed point of the colour
+    """Size-independent properties at BASELINE's 3840x2160 (each stage against the oracle at this size, in its long-band launch geometry:
+    tests/test_gpu_fullsize_parity.py): (1) all-sky frame -> clamped copy; (2) uniform colour on a flat surface is a fixed point of the colour
     channels and variance follows v(1+sum g^2)/(1+sum g)^2; (3) two strips tile the whole frame bitwise."""
     import torch
     from svgf_amd import filter as F

@@ -17,6 +17,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from svgf_amd import synth
 
 
+def band_rows(W, H, S, num_cus=256):
+    """Decimated rows per band of atrous_lds_kernel at step S on a W x H frame (svgf_atrous_lds.h:cut_bands: workgroups resident per CU by LDS and
+    atrous_waves, 4x oversubscribed, no band under 8 rows, a whole number of 2-row steps).  tests/test_launch_geometry.py pins it."""
+    per_cu = 5 if S <= 8 else {16: 4, 32: 3, 64: 2}[S]
+    xt = (W + 127) // 128
+    njmax = (H + S - 1) // S
+    nb = max(1, per_cu * num_cus * 4 // (xt * S))
+    band = max(8, (njmax + nb - 1) // nb); band = (band + 1) // 2 * 2
+    return band
+
+
 def emulate(W=3840, H=2160, steps=(1, 2, 4, 8, 16), scene="planar", verbose=False):
     """-> {step: {rule: share of the wave-steps that hold a surface pixel and would take the uniform-normal path}}."""
     sc = synth.make_scene(W, H, 0, scene=scene)
@@ -35,15 +46,9 @@ def emulate(W=3840, H=2160, steps=(1, 2, 4, 8, 16), scene="planar", verbose=Fals
             a, b = max(0, lo_fn(t)), min(W, hi_fn(t))
             mn[:, t] = kmin[:, a:b].min(1); mx[:, t] = kmax[:, a:b].max(1)
         return mn, mx
-    def band_rows(S):
-        per_cu = 5 if S <= 8 else 4
-        njmax = (H + S - 1) // S
-        nb = max(1, per_cu * 256 * 4 // (xt * S))
-        band = max(8, (njmax + nb - 1) // nb); band = (band + 1) // 2 * 2
-        return band
     res = {}
     for S in steps:
-        band = band_rows(S)
+        band = band_rows(W, H, S)
         wins = {"wg": colwin(lambda t: t*TX - 2*S, lambda t: t*TX + TX + 2*S),
                 "h0": colwin(lambda t: t*TX - 2*S, lambda t: t*TX + 64 + 2*S),
                 "h1": colwin(lambda t: t*TX + 64 - 2*S, lambda t: t*TX + TX + 2*S)}
