@@ -2,6 +2,7 @@
 
     python -m tests.fuzz_parity --minutes 10 --seed 1000 [--kinds stage,strips,driver,rows,pair,post,stage0,negzero,strips2,driver2,wide,widestrips,edge,edgedriver,edgestrips,graph,fullsize] [--out gpurun_out/fuzz.txt]
     python -m tests.fuzz_parity --minutes 30 --seed 1300000 --kinds bigstage          (not in the default list: it would move the kind a seed maps to)
+    python -m tests.fuzz_parity --minutes 20 --seed 1400000 --kinds motion            (likewise)
 
 Each trial draws a frame size (down to 1 x 1, up past the 128-pixel tile and the 64-lane wave in both directions), a storage format, the
 tunables over the GUI's ranges (GUI.cpp:988-993), a camera motion, optionally NaN / inf radiance texels and poisoned G-buffer texels
@@ -29,6 +30,9 @@ tunables over the GUI's ranges (GUI.cpp:988-993), a camera motion, optionally Na
   fullsize   1920x1080 and 3840x2160: strip driver and frame driver under a setting against the plain frame driver, bit for bit, poisoned frames;
   bigstage   one a-trous stage call against the ORACLE at 1920x1080 .. 7680x4320, where the streaming kernel cuts bands longer than its 8-row
            floor (tests/launch_geometry.py): storage, step, tunables, scene (planar / curved), NaN / inf texels and -0.0 blocks drawn at random;
+  motion   per-pixel motion from a moving camera (tests/camera_scene.py: path, size, storage, tunables, poisoning drawn at random): the
+           temporal stage against the ORACLE, raw bits, over the sequence; the frame driver under a random setting against the stage calls,
+           bit for bit, and svgf_adaptive_moments_sample against its host restatement;
   stage0   `stage` with -0.0, denormals and the storage type's extremes in the colour and moments planes;
   negzero  `stage0` with rectangles of -0.0 (inside, across the border, over the whole frame) and a tenth of all texels -0.0 in one channel;
   post     the stages after the path: TAA + sRGB against the oracle and tiled against per-pixel, albedo (de)modulation bit-exact.
@@ -48,8 +52,8 @@ from svgf_amd import synth
 from tests.gbuffer_poison import poison_gbuffer
 from tests.helpers import CDT, gbuf
 
-KINDS = ("stage", "strips", "driver", "rows", "pair", "post", "stage0", "negzero", "strips2", "driver2", "wide", "widestrips", "edge", "edgedriver", "edgestrips", "graph", "fullsize", "bigstage")
-DEFAULT_KINDS = KINDS[:-1]        # (bigstage runs only when asked for: with it the default list would map every CLI seed to another kind)
+KINDS = ("stage", "strips", "driver", "rows", "pair", "post", "stage0", "negzero", "strips2", "driver2", "wide", "widestrips", "edge", "edgedriver", "edgestrips", "graph", "fullsize", "bigstage", "motion")
+DEFAULT_KINDS = KINDS[:-2]        # (bigstage and motion run only when asked for: with them the default list would map every CLI seed to another kind)
 
 
 def _size(rng):
@@ -884,7 +888,68 @@ def trial_bigstage(G, oracle, seed):
     return desc
 
 
-TRIALS = {"bigstage": trial_bigstage, "fullsize": trial_fullsize, "graph": trial_graph, "edgestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, edge=True), "edgedriver": lambda G, oracle, seed: trial_driver(G, oracle, seed, edge=True), "edge": lambda G, oracle, seed: trial_stage(G, oracle, seed, edge=True), "wide": lambda G, oracle, seed: trial_stage(G, oracle, seed, wide=True), "widestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, wide=True),
+def trial_motion(G, oracle, seed):
+    import torch
+    from svgf_amd import filter as F
+    from tests import camera_scene as cs
+    rng = np.random.default_rng(seed)
+    path = str(rng.choice(cs.PATHS))
+    W, H = int(rng.integers(9, 700)), int(rng.integers(9, 400))
+    storage = ("f32", "f16")[int(rng.integers(0, 2))]
+    tun = _tunables(rng)
+    poison = bool(rng.integers(0, 3) == 0)
+    N = int(rng.integers(4, 10))
+    setting = str(rng.choice(["default", "prev_guide", "in_flight", "pair", "adaptive_off"]))
+    if poison and setting == "pair":
+        setting = "default"         # (the pair launch is bit-identical on finite input only: kind `pair` bounds it on poisoned input)
+    desc = f"motion seed {seed}: {path} {W}x{H} {storage} frames {N} poison {poison} setting {setting} {tun}"
+    fr = [dict(f) for f in cs.sequence(path, W, H, N)]
+    if poison:
+        for k in range(N):
+            if rng.integers(0, 2):
+                fr[k] = _poisoned(rng, fr[k], ("motion", "depth", "ddepth", "normal", "id"))
+            if rng.integers(0, 2):
+                fr[k] = dict(fr[k], radiance=_sprinkle(rng, fr[k]["radiance"].copy(), 4))
+    gbs = [G.gb_dev(f) for f in fr]
+    # a. temporal against the oracle from identical inputs
+    ref = oracle.Pipeline(W, H, storage, steps=0, nthreads=8, **tun)
+    t = F.Denoiser(W, H, F.Params(storage=storage, **tun))
+    hip = G.HipPipeline(W, H, storage, steps=5, **tun)
+    d = F.Denoiser(W, H, F.Params(storage=storage, steps=5, **tun))
+    if setting == "prev_guide":
+        d.set_prev_guide(True)
+    elif setting == "in_flight":
+        d.set_frames_in_flight(2)
+    elif setting == "pair":
+        d.set_iteration_fusion(True)
+    elif setting == "adaptive_off":
+        d.set_adaptive_moments(False)
+    try:
+        for k in range(N):
+            kp = max(k - 1, 0)
+            ref.frame(fr[k]["radiance"], gbuf(fr[k]), gbuf(fr[kp]))
+            r = ref.taps
+            col, hist, mom = t.new_colour(), t.new_history(), t.new_moments()
+            t.TemporalFilter(G.dev(r["prev_colour"]), G.dev(r["radiance"]), col, gbs[k], gbs[kp], G.dev(r["prev_hist"]), hist, mom, G.dev(r["prev_mom"]))
+            assert np.array_equal(G.host(hist), r["hist"]), desc + f": frame {k}: temporal history"
+            assert _same_bits(G.host(col), r["temporal"]) and _same_bits(G.host(mom), r["mom"]), desc + f": frame {k}: temporal colour / moments"
+            # d. the frame driver against the stage calls, and the sample it publishes
+            want = hip.frame(fr[k]["radiance"], gbs[k], gbs[kp])
+            got = d.Render(G.dev(fr[k]["radiance"].astype(G.NPDT[storage])), gbs[k], gbs[k - 1] if k else None)
+            d.sync()
+            torch.cuda.synchronize()
+            assert np.array_equal(G.host(got).view(np.uint8), want.view(np.uint8)), desc + f": frame {k}: frame driver"
+            if k >= 1:
+                want_s = cs.young_sample(cs.listed_young(prev_hist, fr[k - 1]["normal"], tun["phi_normal"])) if k >= 4 else (0, 0)
+                assert d.adaptive_moments_sample() == want_s, desc + f": frame {k}: sample {d.adaptive_moments_sample()} != {want_s}"
+            prev_hist = hip.taps["hist"]
+    finally:
+        t.close()
+        d.close()
+    return desc
+
+
+TRIALS = {"motion": trial_motion, "bigstage": trial_bigstage, "fullsize": trial_fullsize, "graph": trial_graph, "edgestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, edge=True), "edgedriver": lambda G, oracle, seed: trial_driver(G, oracle, seed, edge=True), "edge": lambda G, oracle, seed: trial_stage(G, oracle, seed, edge=True), "wide": lambda G, oracle, seed: trial_stage(G, oracle, seed, wide=True), "widestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, wide=True),
           "driver2": trial_driver2, "strips2": trial_strips2, "stage0": lambda G, oracle, seed: trial_stage(G, oracle, seed, zeros=True), "negzero": lambda G, oracle, seed: trial_stage(G, oracle, seed, zeros=2), "stage": trial_stage, "strips": trial_strips, "driver": trial_driver, "rows": trial_rows, "pair": trial_pair, "post": trial_post}
 
 
