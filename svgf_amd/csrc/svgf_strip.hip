@@ -15,8 +15,10 @@
 //   per-iteration  [[0],[1],[2],[3],[4]]    the literal "halo exchange between à-trous iterations"
 // The temporal and moments stages run redundantly on the first group's halo, so a frame needs one more exchange: its STATE
 // (colour feedback, moments, history) on the rows the next frame's reprojection can reach.  That state is final once
-// iteration 0 has written the feedback colour: it is posted right there and waited for at the start of the NEXT frame — the
-// transfer runs beside iterations 1.. of the frame that produced it.
+// iteration 0 has written the feedback colour and is waited for at the start of the NEXT frame: the transfer runs beside
+// iterations 1.. of the frame that produced it.  Schedule: behind the temporal launches, frame_schedule decides every a-trous launch
+// step of a frame before the first is enqueued (the iterations, the exchange waited for, the rows produced first and in which launches,
+// what is posted behind them, the move to the side stream), and run_step carries each out on every local rank.
 //
 // A driver object holds the strips of the ranks that live in THIS process: one (a rank per process, the bench.py layout),
 // several on several devices (one host process driving the node, ncclCommInitAll-style), or several virtual ranks on one
@@ -122,20 +124,17 @@ struct svgf_strips {
         // (svgf_ctx).  The launches, the exchanges' ready records and their waits go to ctx->stream: `compute`, or the side stream for a frame's tail.
         Event ready, halo_done, state_done;
         Event mb_ready, mb_done;                               // mailbox: this rank's communication stream has reached the group / has received what the group sends it
-        // edge rows first (svgf_strips_set_edge_first): the iteration in front of an exchange is ONE launch whose first workgroups produce the rows the
-        // neighbours wait for; the last of them writes edge_value into its slot's signal word and the communication stream waits for that word
-        // (hipStreamWaitValue64) instead of for an event behind two extra launches
-        // Two slots: launches on the filter stream use slot 0, launches on the side stream (two frames in flight: a frame's tail) slot 1 —
+        // edge rows first (svgf_strips_set_edge_first, Form::Ranges): the last of the first workgroups of the launch in front of an exchange writes
+        // edge_value into its slot's signal word, and the communication stream waits for that word (hipStreamWaitValue64, Wait::Signal)
+        // Two slots (signal_slot): launches on the filter stream use slot 0, launches on the side stream (two frames in flight: a frame's tail) slot 1 —
         // the two streams run CONCURRENTLY, and a word (or an arrival counter) shared between them is written out of order: the wait for the
         // smaller sequence number passes early and the one for the larger never (round 5's first version hung exactly there).
         // The two signal words are HSA signal memory (hipExtMallocWithFlags(hipMallocSignalMemory): what hipStreamWaitValue64 is documented for; plain
         // device memory works on this ROCm build too — tools/ubench/wait_value.hip — but is not promised), the arrival counters plain device memory.
-        // No signal memory: edge_signal stays null and every exchanging iteration keeps the three-launch schedule.
+        // No signal memory: edge_signal stays null and frame_schedule chooses no ranges launch.
         DevicePtr<unsigned long long> edge_signal[2];
         DevicePtr<unsigned> edge_arrivals;                     // two counters, 256 B apart
-        unsigned long long edge_value[2] = {0, 0};
-        int edge_slot = 0;                                     // the slot of the launch just enqueued
-        bool edge_pending = false;                             // the launch just enqueued signals: the next exchange waits for edge_value[edge_slot]
+        unsigned long long edge_value[2] = {0, 0};             // what the last launch of each slot writes
         bool state_pending = false;
         // the host never runs more than kMaxAhead frames ahead of the device: frame f waits for the end of frame f - kMaxAhead.  With ~100
         // frames of launches, events and RCCL groups queued the device starts to starve (0.43 -> 0.6 ms per 8K/8 strip, tools/strip_sim.py)
@@ -358,32 +357,39 @@ int group_failed(svgf_strips* s, int rc) {
     return sfail(s, rc, why + " (the strip driver is unusable from here: destroy it)");
 }
 
+// the signal slot of the launches rank l enqueues now: 0 on its filter stream, 1 on the side stream (Local::edge_signal)
+int signal_slot(const svgf_strips::Local& l) { return l.ctx->stream == l.compute ? 0 : 1; }
+
+// What the transfers of an exchange wait for, as its caller knows: nothing (the rows were final before the exchange posted last started, and
+// the communication stream runs in order), the signal word of the ranges launch every rank has just enqueued (its edge rows), or the `ready`
+// event recorded behind everything enqueued so far.
+enum class Wait { InOrder, Signal, Ready };
+
 // Post ONE exchange for all local ranks: for every plane of `planes` the rows at distance [held, h) from each strip boundary (exchange_msgs).
 // is_state selects which event the filter stream will wait for.
-// in_order: the rows this exchange carries were final before the exchange posted last started (the communication stream runs in order: nothing to wait for)
-int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, bool is_state, bool in_order = false) {
+int post_exchange(svgf_strips* s, const std::vector<PlaneSpec>& planes, int h, bool is_state, Wait wait) {
     const Transport& T = transport_of(s);
     // The transfers of a rank start when its filter stream has produced the rows it sends and is done with the halo rows it
     // receives into.  Loop-back: every virtual rank shares one communication stream, which then waits for all of them.
     // (An event record is a barrier packet on the filter stream — ~6 us between two launches that would otherwise run back to back,
     // profiles/r05_strip_trace_*.txt: it is only recorded where something will wait for it.)
-    for (auto& l : s->local) {
+    if (wait == Wait::Ready) for (auto& l : s->local) {
         DeviceGuard dg(l.device);
-        if (!in_order && !l.edge_pending) SVGF_SHIP(s, hipEventRecord(l.ready.get(), l.ctx->stream));
+        SVGF_SHIP(s, hipEventRecord(l.ready.get(), l.ctx->stream));
     }
-    // (edge rows first: the rows a rank sends are final when the first workgroups of the launch it has just enqueued have signalled — the
+    // (Signal: the rows a rank sends are final when the first workgroups of the launch it has just enqueued have signalled — the
     // communication stream waits for that word, not for the launch; everything enqueued BEFORE that launch is complete by then, stream order)
     auto wait_for = [&](svgf_strips::Local& on, svgf_strips::Local& of) -> int {
-        if (of.edge_pending) SVGF_SHIP(s, hipStreamWaitValue64(on.comm_stream, of.edge_signal[of.edge_slot].get(), of.edge_value[of.edge_slot], hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull));
+        const int k = signal_slot(of);
+        if (wait == Wait::Signal) SVGF_SHIP(s, hipStreamWaitValue64(on.comm_stream, of.edge_signal[k].get(), of.edge_value[k], hipStreamWaitValueGte, 0xFFFFFFFFFFFFFFFFull));
         else SVGF_SHIP(s, hipStreamWaitEvent(on.comm_stream, of.ready.get(), 0));
         return SVGF_OK;
     };
-    if (!in_order) for (auto& l : s->local) {
+    if (wait != Wait::InOrder) for (auto& l : s->local) {
         DeviceGuard dg(l.device);
         if (!s->loopback) { if (int rc = wait_for(l, l); rc != SVGF_OK) return rc; }
         else if (&l == &s->local[0]) for (auto& m : s->local) { if (int rc = wait_for(l, m); rc != SVGF_OK) return rc; }
     }
-    for (auto& l : s->local) l.edge_pending = false;
     if (int rc = T.group_start(s); rc != SVGF_OK) return rc;
     struct Post { svgf_strips::Local* l; MsgSpec m; };
     std::vector<Post> posts;
@@ -430,14 +436,53 @@ int wait_exchange(svgf_strips* s, svgf_strips::Local& l, bool is_state) {
     return SVGF_OK;
 }
 
-// pair: iterations 0 and 1 in one launch on `rows` (iteration 1's; iteration 0 and the feedback store cover 4 rows more either side)
-// inner != nullptr: ONE launch over the two edge ranges [rows.a, inner->a), [inner->b, rows.b) — produced first and signalled — and the interior *inner
-int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src, int dst, int P, const svgf_gbuffer* cur, int i, bool pair = false, const Rows* inner = nullptr,
-                       const Rows* left_out = nullptr) {
-    if (rows.b <= rows.a) return SVGF_OK;
+// the frame's state (colour feedback, moments, history) on the rows the next frame's reprojection can reach (state_planes)
+int post_state(svgf_strips* s, Wait wait) {
+    const svgf_strip_plan_geo& g = s->local[0].g;
+    return post_exchange(s, state_planes(g, s->steps, s->local[0].ctx->pingpong), g.halo_state, true, wait);   // (all local contexts advance together)
+}
+
+// How a step produces its rows: one launch; the two edge ranges in launches of their own, the exchange behind an event, the interior; or ONE launch
+// of the edge ranges first and signalled and the head of the interior, the exchange behind the signal, the rest of the interior
+enum class Form { Whole, Edges, Ranges };
+
+struct Step {
+    int iter = 0;
+    bool pair = false;                // iterations 0 and 1 in one launch (svgf_atrous_pair) on iteration 1's rows
+    bool wait_filter = false;         // the exchange of filter rows an earlier step posted is waited for first
+    int reach = 0;                    // the rows within `reach` of each boundary with a neighbour are produced first (0: none, Form::Whole)
+    Form form = Form::Whole;
+    int head_percent = 0;             // Form::Ranges: the share of the interior that goes with the edge rows
+    int filter_reach = 0; Wait filter_wait = Wait::Ready;   // the exchange of filter rows posted behind the edge rows (reach 0: none) and what it waits for
+    bool state = false; Wait state_wait = Wait::Ready;     // the state exchange, posted behind the filter exchange (InOrder), the signalled edge rows (Signal) or the whole step (Ready)
+    bool fork = false;                // the steps after this one go to the side stream of every rank (two frames in flight)
+};
+
+// Rank l's rows of step st as its launches cover them: the two edge ranges (empty without a reach), the head of the interior (Form::Whole: all
+// the rows) and the rest of the interior, which follows the exchange
+struct Cut { Rows top, bottom, head, rest; };
+Cut cut_rows(const svgf_strips* s, const svgf_strips::Local& l, const Step& st) {
+    const Rows rows = grown(l.g, s->H, l.g.ext_atrous[st.pair ? 1 : st.iter]);     // (the pair: iteration 0 runs on 4 rows more either side inside it)
+    if (!st.reach) return Cut{{rows.a, rows.a}, {rows.b, rows.b}, rows, {rows.b, rows.b}};
+    const int lo = l.rank == 0 ? rows.a : std::min(rows.b, l.g.own0 + st.reach);
+    const int hi = l.rank == s->world - 1 ? rows.b : std::max(rows.a, l.g.own1 - st.reach);
+    const int mid = lo + (int)((long long)(hi - lo) * st.head_percent / 100);
+    return Cut{{rows.a, lo}, {hi, rows.b}, {lo, mid}, {mid, hi}};
+}
+
+// One a-trous launch of step st on rank l over the non-empty ones of the ranges given: `first` produced first and signalled (ONE ranges launch,
+// svgf_kernels.h: AtrousRanges — what Wait::Signal waits for), `then` behind them; no `first`: a plain launch over `then`.  Timed over the rows it covers.
+int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, const Step& st, int src, const svgf_gbuffer* cur, std::initializer_list<Rows> first, Rows then) {
+    svgf::AtrousRanges r{};
+    int rb = then.a, re = then.b, rows = 0;           // (rb, re: the hull of the ranges — the ranges launch reads only the ranges)
+    auto add = [&](Rows x) { rb = std::min(rb, x.a); re = std::max(re, x.b); if (x.b > x.a) { r.yb[r.n] = x.a; r.ye[r.n] = x.b; r.n++; rows += x.b - x.a; } };
+    for (Rows x : first) add(x);
+    r.nfirst = r.n;
+    add(then);
+    if (!rows) return SVGF_OK;
     svgf_ctx* c = l.ctx;
     DeviceGuard dg(l.device);
-    c->rb = rows.a; c->re = rows.b;
+    c->rb = rb; c->re = re;
     const bool timed = s->timing_every > 0 && ((s->frame_no - s->timing_base) % s->timing_every) == 0 && l.rank == s->local[0].rank;
     Event e0, e1;
     if (timed) {
@@ -446,26 +491,110 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, Rows rows, int src
         SVGF_SHIP(s, hipEventRecord(e0.get(), c->stream));
     }
     const void* guide = use_guide(c) ? c->guide.get() : nullptr;
+    const void* in = c->filter[src].get(); void* out = c->filter[1 - src].get();
+    void* feedback = st.iter == 0 ? c->colour[c->pingpong].get() : nullptr;
     int rc = SVGF_OK;
-    if (inner) {
-        svgf::AtrousRanges r{};
-        auto add = [&](int a, int b) { if (b > a) { r.yb[r.n] = a; r.ye[r.n] = b; r.n++; } };
-        add(rows.a, inner->a); add(left_out ? left_out->b : inner->b, rows.b);        // (left_out: interior rows [inner->b, left_out->b) go into the NEXT launch)
-        r.nfirst = r.n;
-        add(inner->a, inner->b);
-        const int slot = c->stream == l.compute ? 0 : 1;
-        r.signal = l.edge_signal[slot].get(); r.arrivals = l.edge_arrivals.get() + 64 * slot; r.value = ++l.edge_value[slot];
-        rc = atrous_ranges_impl(c, c->filter[src].get(), c->filter[dst].get(), i == 0 ? c->colour[P].get() : nullptr, cur, 1 << i, i, guide, r);
-        if (rc == SVGF_OK) { l.edge_pending = r.nfirst > 0; l.edge_slot = slot; }
-    } else rc = pair ? atrous_pair_impl(c, c->filter[src].get(), c->filter[dst].get(), c->colour[P].get(), cur, guide)
-                     : atrous_impl(c, c->filter[src].get(), c->filter[dst].get(), i == 0 ? c->colour[P].get() : nullptr, cur, 1 << i, i, guide);
+    if (first.size()) {
+        const int k = signal_slot(l);
+        r.signal = l.edge_signal[k].get(); r.arrivals = l.edge_arrivals.get() + 64 * k; r.value = ++l.edge_value[k];
+        rc = atrous_ranges_impl(c, in, out, feedback, cur, 1 << st.iter, st.iter, guide, r);
+    } else rc = st.pair ? atrous_pair_impl(c, in, out, feedback, cur, guide) : atrous_impl(c, in, out, feedback, cur, 1 << st.iter, st.iter, guide);
     if (rc != SVGF_OK) return sfail(s, rc, c->err);
     if (timed) {
         SVGF_SHIP(s, hipEventRecord(e1.get(), c->stream));
         l.tev.push_back(std::move(e0)); l.tev.push_back(std::move(e1));
-        // (rows of the interior that were left to the NEXT launch are that launch's: left_out)
-        l.tbytes_px.push_back((double)((rows.b - rows.a) - (inner && left_out ? left_out->b - left_out->a : 0)) * s->W);
-        l.titer.push_back(pair ? -1 : i);
+        l.tbytes_px.push_back((double)rows * s->W);
+        l.titer.push_back(st.pair ? -1 : st.iter);
+    }
+    return SVGF_OK;
+}
+
+// Edge rows first in front of an exchange of filter rows: the share of the interior in the signalled launch (the rest is a launch of its own behind
+// the exchange's post).  An exchange's kernel (one RCCL workgroup: 132 registers per thread, 20 KB of LDS) finds no room beside a launch that
+// oversubscribes every CU and so completed when the iteration drained: ~20 us of idle filter stream per exchange (profiles/r05_strip_trace_*.txt).
+// Between the two launches the chip drains for a moment and the exchange gets its CU.  (20 / 33 / 50 measure the same within 1 %, 66 leaves it too little time.)
+constexpr int kHeadPercent = 33;
+
+// The launch steps of one frame, all decided before the first is enqueued.
+// The exchange in front of iteration group g + 1 carries the rows within halo_group[g + 1] of every strip boundary of the LAST iteration of group g.
+// That iteration produces those rows FIRST, the exchange is posted behind them and the interior follows: the transfer runs beside that interior and
+// has landed when the next group's first iteration, which waits for it and covers all of its rows in one launch, starts.  (Round 3 posted the exchange
+// after the WHOLE previous iteration: the tail of the producing iteration and the head of the consuming one were serialised with the transfer.)  The
+// edge rows are two launches of their own (Form::Edges) or — edge rows first, opt-in, where every local rank can run it — the signalled head of ONE
+// launch (Form::Ranges: no event, no extra launches' ramp and tail).  A strip no taller than its two edges keeps one launch, the exchange behind it.
+// The state exchange is final once iteration 0 has written the feedback colour.  The communication stream runs in order, so it is posted BEHIND the
+// frame's last exchange of filter rows (in front of them it delayed the exchange the next iteration waits for: 23 us of idle filter stream in the
+// trace), with no wait of its own if that exchange carries rows of an iteration >= 1 (it started after iteration 0).  Otherwise it is posted behind
+// iteration 0 — with edge rows first and no exchange of filter rows, behind the state's rows produced first and signalled, the whole interior in the
+// same launch (nobody waits for the state exchange before the next frame).  Two frames in flight: after iteration 0 and its exchanges the rest of
+// the frame goes to the side stream of every rank, if it may (tail_may_leave).
+std::vector<Step> frame_schedule(const svgf_strips* s) {
+    const svgf_strip_plan_geo& g = s->local[0].g;
+    const auto& groups = g.groups;
+    const bool exchanging = s->world > 1;
+    int last_feed = -1;                   // the iteration whose rows the frame's last exchange of filter rows carries (-1: none)
+    for (size_t gi = 0; exchanging && gi + 1 < groups.size(); gi++) last_feed = groups[gi].back();
+    auto every_rank = [&](auto f) { return std::all_of(s->local.begin(), s->local.end(), f); };
+    const bool tail_ok = s->frames_in_flight > 1 && every_rank([](const svgf_strips::Local& l) { return tail_may_leave(l.ctx, 1); });
+    auto ranges_ok = [&](int i) {          // edge rows first, and every local rank can run the ranges launch of iteration i
+        return s->edge_first && every_rank([&](const svgf_strips::Local& l) { return atrous_ranges_ok(l.ctx, 1 << i) && l.edge_signal[0] != nullptr; });
+    };
+    auto fits = [&](Step st, int reach) {  // every local strip is taller than its two edges of that reach
+        st.reach = reach; st.head_percent = 0;
+        return every_rank([&](const svgf_strips::Local& l) { const Cut c = cut_rows(s, l, st); return c.rest.b > c.rest.a; });
+    };
+    std::vector<Step> steps;
+    for (size_t gi = 0; gi < groups.size(); gi++)
+        for (size_t q = 0; q < groups[gi].size(); q++) {
+            Step st;
+            st.iter = groups[gi][q];
+            st.wait_filter = exchanging && gi > 0 && q == 0;
+            st.pair = st.iter == 0 && q + 1 < groups[gi].size() && groups[gi][q + 1] == 1 && can_fuse01(s->local[0].ctx);
+            if (st.pair) q++;
+            if (exchanging && q + 1 == groups[gi].size() && gi + 1 < groups.size()) {
+                st.filter_reach = g.halo_group[gi + 1];
+                if (!st.pair && fits(st, st.filter_reach)) {
+                    const bool one = ranges_ok(st.iter);
+                    st.reach = st.filter_reach; st.form = one ? Form::Ranges : Form::Edges; st.head_percent = one ? kHeadPercent : 0;
+                }
+                st.filter_wait = st.form == Form::Ranges ? Wait::Signal : Wait::Ready;
+            }
+            if (last_feed >= 1 && groups[gi][q] == last_feed) { st.state = true; st.state_wait = Wait::InOrder; }
+            else if (exchanging && last_feed < 1 && st.iter == 0) {
+                st.state = true;
+                if (last_feed < 0 && !st.pair && ranges_ok(0) && fits(st, g.halo_state)) {
+                    st.reach = g.halo_state; st.form = Form::Ranges; st.head_percent = 100; st.state_wait = Wait::Signal;
+                }
+            }
+            st.fork = st.iter == 0 && tail_ok;
+            steps.push_back(st);
+        }
+    return steps;
+}
+
+// Step st on every local rank.  pp[k]: the filter plane of rank k that holds the step's input; on return, the one that holds its output.
+int run_step(svgf_strips* s, const Step& st, const svgf_gbuffer* cur, std::vector<int>& pp) {
+    const int n = (int)s->local.size();
+    if (st.wait_filter) for (auto& l : s->local) if (int rc = wait_exchange(s, l, false); rc != SVGF_OK) return rc;
+    std::vector<Cut> cut(n);
+    for (int k = 0; k < n; k++) {
+        auto& l = s->local[k];
+        const Cut& c = cut[k] = cut_rows(s, l, st);
+        int rc = SVGF_OK;
+        if (st.form == Form::Ranges) rc = launch_atrous_rows(s, l, st, pp[k], &cur[k], {c.top, c.bottom}, c.head);
+        else for (Rows rows : {c.top, c.bottom, c.head}) if (rc == SVGF_OK) rc = launch_atrous_rows(s, l, st, pp[k], &cur[k], {}, rows);
+        if (rc != SVGF_OK) return rc;
+    }
+    if (st.filter_reach) if (int rc = post_exchange(s, {{SVGF_PLANE_FILTER, 1 - pp[0], 0}}, st.filter_reach, false, st.filter_wait); rc != SVGF_OK) return rc;
+    if (st.state && st.state_wait != Wait::Ready) if (int rc = post_state(s, st.state_wait); rc != SVGF_OK) return rc;
+    for (int k = 0; k < n; k++) {
+        if (int rc = launch_atrous_rows(s, s->local[k], st, pp[k], &cur[k], {}, cut[k].rest); rc != SVGF_OK) return rc;
+        pp[k] ^= 1;
+    }
+    if (st.state && st.state_wait == Wait::Ready) if (int rc = post_state(s, Wait::Ready); rc != SVGF_OK) return rc;
+    if (st.fork) for (auto& l : s->local) {
+        DeviceGuard dg(l.device);
+        if (int rc = fork_side(l.ctx); rc != SVGF_OK) return sfail(s, rc, l.ctx->err);
     }
     return SVGF_OK;
 }
@@ -733,142 +862,12 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         // of the later iteration groups and the next frame's reprojection read them)
         if (rc != SVGF_OK) return sfail(s, rc, c->err);
     }
-    // The state exchange: final once iteration 0 has written the feedback colour, needed by the NEXT frame's temporal launch.  The communication stream
-    // runs in order, so it is posted BEHIND the frame's last exchange of filter rows (in front of them it delayed the exchange the next iteration
-    // waits for: 23 us of idle filter stream in the trace) — and needs no wait of its own there: an exchange posted for an iteration >= 1 started
-    // after rows of that iteration were done, i.e. after iteration 0.  A frame without such an exchange posts it right behind iteration 0.
-    int last_feed = -1;
-    {
-        const auto& gr = s->local[0].g.groups;
-        for (size_t gi = 0; gi + 1 < gr.size(); gi++) last_feed = gr[gi].back();
-        if (s->world <= 1) last_feed = -1;
-    }
-    auto post_state = [&](bool in_order) -> int {
-        if (s->world <= 1) return SVGF_OK;
-        const svgf_strip_plan_geo& g = s->local[0].g;
-        const int P = s->local[0].ctx->pingpong;           // all local contexts advance together
-        return post_exchange(s, state_planes(g, s->steps, P), g.halo_state, true, in_order);
-    };
-    // Two frames in flight: once iteration 0 has stored the feedback colour and the state exchange is posted, iterations 1.. (their exchanges
-    // included) go to the side stream of every rank, if they may (tail_may_leave) — the frame that was there is ordered on the filter stream first.
-    bool tail_ok = s->frames_in_flight > 1;
-    for (int k = 0; k < n && tail_ok; k++) tail_ok = tail_may_leave(s->local[k].ctx, 1);
+    if (!s->steps && s->world > 1) if (int rc = post_state(s, Wait::Ready); rc != SVGF_OK) return rc;   // (no iterations: the state is final here)
     bool aside = false;
-    auto fork_every_rank = [&]() -> int {
-        for (int k = 0; k < n && tail_ok; k++) {
-            DeviceGuard dg(s->local[k].device);
-            if (int rc = fork_side(s->local[k].ctx); rc != SVGF_OK) return sfail(s, rc, s->local[k].ctx->err);
-        }
-        aside = tail_ok;
-        return SVGF_OK;
-    };
-    const auto& groups = s->local[0].g.groups;
-    // The exchange in front of iteration group g + 1 carries the rows within halo_group[g + 1] of every strip boundary of the LAST
-    // iteration of group g.  That iteration therefore produces those rows FIRST (two edge launches), the exchange is posted behind
-    // them, and the interior follows: the transfer runs beside the interior of the iteration that produced its rows — and has landed
-    // when the next group's first iteration, which waits for it and then covers all of its rows in one launch, starts.  (Round 3 posted
-    // the exchange after the WHOLE previous iteration and ran the next iteration's interior beside it: the tail of the producing
-    // iteration and the head of the consuming one were serialised with the transfer.)
-    bool posted = false;                              // an exchange of filter rows is in flight for the group about to start
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        for (size_t q = 0; q < groups[gi].size(); q++) {
-            const int i = groups[gi][q];
-            if (q == 0 && posted) {
-                for (int k = 0; k < n; k++) { int rc = wait_exchange(s, s->local[k], false); if (rc != SVGF_OK) return rc; }
-                posted = false;
-            }
-            // iterations 0 and 1 of one group: ONE launch on iteration 1's rows (svgf_atrous_pair); iteration 0 runs on 4 rows more
-            // either side — grown(ext_atrous[0]) exactly — inside it
-            if (i == 0 && q + 1 < groups[gi].size() && groups[gi][q + 1] == 1 && can_fuse01(s->local[0].ctx)) {
-                for (int k = 0; k < n; k++) {
-                    auto& l = s->local[k];
-                    int rc = launch_atrous_rows(s, l, grown(l.g, s->H, l.g.ext_atrous[1]), pp[k], 1 - pp[k], l.ctx->pingpong, &cur[k], 0, true);
-                    if (rc != SVGF_OK) return rc;
-                    pp[k] ^= 1;
-                }
-                int rc = last_feed < 1 ? post_state(false) : SVGF_OK;
-                if (rc == SVGF_OK) rc = fork_every_rank();
-                if (rc != SVGF_OK) return rc;
-                q++;
-                if (q + 1 == groups[gi].size() && gi + 1 < groups.size() && s->world > 1) {      // (a group of exactly {0, 1}: its output travels whole)
-                    rc = post_exchange(s, {{SVGF_PLANE_FILTER, pp[0], 0}}, s->local[0].g.halo_group[gi + 1], false);
-                    if (rc == SVGF_OK && last_feed == 1) rc = post_state(true);
-                    if (rc != SVGF_OK) return rc;
-                    posted = true;
-                }
-                continue;
-            }
-            const bool feeds_exchange = q + 1 == groups[gi].size() && gi + 1 < groups.size() && s->world > 1;
-            // iteration 0 of a frame whose STATE exchange is posted right behind it (no exchange of filter rows later in the frame: the ghost plan): the rows
-            // the state exchange carries — within halo_state of the boundaries — are produced first and signalled like the rows of any other exchange
-            const bool feeds_state = i == 0 && last_feed < 1 && s->world > 1 && !feeds_exchange && s->edge_first;
-            const int h = feeds_exchange ? s->local[0].g.halo_group[gi + 1] : feeds_state ? s->local[0].g.halo_state : 0;
-            std::vector<Rows> inner(n, Rows{0, 0});
-            bool split = feeds_exchange || feeds_state;
-            if (split) {
-                for (int k = 0; k < n; k++) {            // the rows the neighbours will need (the last iteration of a group runs on the owned rows)
-                    auto& l = s->local[k];
-                    const Rows rows = grown(l.g, s->H, l.g.ext_atrous[i]);
-                    const int lo = l.rank == 0 ? rows.a : std::min(rows.b, l.g.own0 + h);
-                    const int hi = l.rank == s->world - 1 ? rows.b : std::max(rows.a, l.g.own1 - h);
-                    inner[k] = Rows{lo, std::max(lo, hi)};
-                    if (hi <= lo) split = false;         // a strip shorter than its two edges: one launch, the exchange behind it
-                }
-            }
-            // edge rows first, in ONE launch (round 5): the launch's first workgroups produce the two edge ranges and signal, the interior follows
-            // in the same launch — instead of two edge launches, the exchange's event, and an interior launch (three launches' ramp and tail)
-            std::vector<Rows> rest(n, Rows{0, 0});
-            bool one_launch = split && s->edge_first;
-            for (int k = 0; k < n && one_launch; k++) one_launch = atrous_ranges_ok(s->local[k].ctx, 1 << i) && s->local[k].edge_signal[0] != nullptr;
-            for (int k = 0; k < n; k++) {
-                auto& l = s->local[k];
-                const Rows rows = grown(l.g, s->H, l.g.ext_atrous[i]);
-                int rc = SVGF_OK;
-                if (one_launch) {
-                    // ... and only the first third of the interior: the rest is a launch of its own BEHIND the exchange's post.  An exchange's kernel
-                    // (one RCCL workgroup: 132 registers per thread, 20 KB of LDS) finds no room beside a launch that oversubscribes every CU — whenever a
-                    // filter workgroup retires, the next one takes its place — and so completed when the iteration drained, with the next iteration
-                    // waiting behind it: ~20 us of idle filter stream per exchange (profiles/r05_strip_trace_*.txt).  At the boundary between the two
-                    // launches the chip drains for a moment, the exchange gets its CU, and it has the second launch to finish in.
-                    constexpr int kHeadPercent = 33;      // (20 / 33 / 50 measure the same within 1 %, 66 leaves the exchange too little time)
-                    rest[k] = Rows{inner[k].a + (int)((long long)(inner[k].b - inner[k].a) * kHeadPercent / 100), inner[k].b};
-                    if (feeds_state) rest[k] = Rows{inner[k].b, inner[k].b};      // (nobody waits for the state exchange before the next frame: one launch)
-                    const Rows head{inner[k].a, rest[k].a};
-                    rc = launch_atrous_rows(s, l, rows, pp[k], 1 - pp[k], l.ctx->pingpong, &cur[k], i, false, &head, &rest[k]);
-                }
-                else if (split) {
-                    rc = launch_atrous_rows(s, l, Rows{rows.a, inner[k].a}, pp[k], 1 - pp[k], l.ctx->pingpong, &cur[k], i);
-                    if (rc == SVGF_OK) rc = launch_atrous_rows(s, l, Rows{inner[k].b, rows.b}, pp[k], 1 - pp[k], l.ctx->pingpong, &cur[k], i);
-                } else rc = launch_atrous_rows(s, l, rows, pp[k], 1 - pp[k], l.ctx->pingpong, &cur[k], i);
-                if (rc != SVGF_OK) return rc;
-            }
-            if (feeds_exchange) {
-                int rc = post_exchange(s, {{SVGF_PLANE_FILTER, 1 - pp[0], 0}}, h, false);
-                if (rc == SVGF_OK && i == last_feed && i >= 1) rc = post_state(true);
-                if (rc != SVGF_OK) return rc;
-                posted = true;
-            }
-            if (one_launch) {
-                split = false;                        // (the interior is part of that launch — and of the one behind it)
-                for (int k = 0; k < n; k++) {
-                    int rc = launch_atrous_rows(s, s->local[k], rest[k], pp[k], 1 - pp[k], s->local[k].ctx->pingpong, &cur[k], i);
-                    if (rc != SVGF_OK) return rc;
-                }
-            }
-            if (split) for (int k = 0; k < n; k++) {
-                auto& l = s->local[k];
-                int rc = launch_atrous_rows(s, l, inner[k], pp[k], 1 - pp[k], l.ctx->pingpong, &cur[k], i);
-                if (rc != SVGF_OK) return rc;
-            }
-            for (int k = 0; k < n; k++) pp[k] ^= 1;
-            if (i == 0) {                             // this frame's state is final once iteration 0 has written the feedback colour
-                int rc = last_feed < 1 ? post_state(false) : SVGF_OK;
-                if (rc == SVGF_OK) rc = fork_every_rank();
-                if (rc != SVGF_OK) return rc;
-            }
-        }
+    for (const Step& st : frame_schedule(s)) {
+        if (int rc = run_step(s, st, cur, pp); rc != SVGF_OK) return rc;
+        aside = aside || st.fork;
     }
-    if (!s->steps) { int rc = post_state(false); if (rc != SVGF_OK) return rc; }
     for (int k = 0; k < n; k++) {
         auto& l = s->local[k];
         svgf_ctx* c = l.ctx;

@@ -257,7 +257,7 @@ class StripRunner:
                     h = None
                 # The last iteration of a group that another group follows produces the rows its neighbours need FIRST (the rows within
                 # the next group's halo of the strip boundaries), posts the exchange behind them and runs its interior beside the transfer
-                # (the schedule of svgf_strips_frame, svgf_amd/csrc/svgf_strip.hip).
+                # (the default schedule, Form::Edges, that frame_schedule in svgf_amd/csrc/svgf_strip.hip decides for the C++ driver).
                 if k + 1 == len(grp) and gi + 1 < len(g.groups) and g.world > 1:
                     hn = g.halo_group[gi + 1]
                     inner, edges = self._split(rows, hn)
