@@ -21,6 +21,13 @@
  *    Colour planes are {r,g,b,variance}, moments planes {E[L],E[L^2]}, in the storage type chosen at
  *    creation: SVGF_F16 = the reference's half4/half2 (Filter.cuh:15-16), SVGF_F32 = float4/float2.
  *    History planes are uint8 (Filter.cuh:359,400).
+ *  - Extent and alignment.  A plane of a context that holds `rows` rows (svgf_create: H; a strip context: strip.rows) is the bytes
+ *    [p, p + rows * W * texel), texel = 16 (motion), 8 (normal, uv), 16 / 8 (colour: SVGF_F32 / SVGF_F16), 8 / 4 (moments), 1 (history).
+ *    `p` is aligned to the plane's texel size, nothing more (no load or store of a kernel is wider than the texel it addresses).  A call
+ *    reads and writes no byte outside those extents — a tap outside the frame, or outside the rows a strip holds, is skipped, never
+ *    fetched — so the planes of one call may be adjacent in memory (sub-allocated from one arena).  Input planes are not written, except
+ *    for the aliases a call documents: radiance == colour_out (svgf_temporal), out == in (svgf_modulate).  Held, inside a caller arena
+ *    with poisoned and with live margins, by tests/test_gpu_plane_isolation.py (tests/plane_arena.py).
  *  - Calls enqueue work on the context's HIP stream and return without synchronising, like the
  *    reference's launches on the default stream (App.cu:471-505).  Errors are returned (0 = ok,
  *    negative = SVGF_ERR_*), never asserted (the reference asserts: App.cu:41-48).  A refused call launches nothing, leaves the

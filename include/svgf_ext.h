@@ -44,7 +44,9 @@ int svgf_temporal_moments(svgf_ctx* ctx, const void* prev_colour, const void* ra
 /* Stage 3, iterations 0 and 1 in ONE launch — the first two trips of the loop in application::WaveletFilter (App.cu:497-507:
  * steps 1 and 2, FilterBuffer[0] -> [1] -> [0]) without the plane in between: iteration 0's rows stay on the chip for iteration 1
  * and reach memory only as `feedback` (RenderOutput, Filter.cuh:619-622; may be NULL).  `out` receives what two svgf_atrous calls
- * would leave in their second `out`, bit for bit, on the rows set by svgf_set_rows; `feedback` is written on those rows and the
+ * would leave in their second `out` on the rows set by svgf_set_rows — bit for bit on input free of NaN, infinite and -0.0 texels;
+ * a band that holds one is computed in the exact form throughout, where the two launches take it per pixel: same NaN mask, zeros
+ * and sky copies, values within 2e-4 x max(1, 50 / PhiColour) (fp32) or 2e-2 (fp16) of theirs; `feedback` is written on those rows and the
  * 4 rows beyond them inside the frame (iteration 1 reads iteration 0 there), so the planes must hold 6 rows around the launch
  * rows (SVGF_ERR_HALO otherwise).  `in`, `out` and `feedback` are three different planes.  Needs variant != SVGF_VARIANT_DIRECT
  * and PhiNormal != 0.  Measured on MI355X the pair launch is ~10 % SLOWER than the two launches it replaces (the iterations are

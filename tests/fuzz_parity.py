@@ -3,6 +3,7 @@
     python -m tests.fuzz_parity --minutes 10 --seed 1000 [--kinds stage,strips,driver,rows,pair,post,stage0,negzero,strips2,driver2,wide,widestrips,edge,edgedriver,edgestrips,graph,fullsize] [--out gpurun_out/fuzz.txt]
     python -m tests.fuzz_parity --minutes 30 --seed 1300000 --kinds bigstage          (not in the default list: it would move the kind a seed maps to)
     python -m tests.fuzz_parity --minutes 20 --seed 1400000 --kinds motion            (likewise)
+    python -m tests.fuzz_parity --minutes 5 --seed 1500000 --kinds arena              (likewise: a `stage` trial with its planes inside one caller arena)
 
 Each trial draws a frame size (down to 1 x 1, up past the 128-pixel tile and the 64-lane wave in both directions), a storage format, the
 tunables over the GUI's ranges (GUI.cpp:988-993), a camera motion, optionally NaN / inf radiance texels and poisoned G-buffer texels
@@ -52,8 +53,8 @@ from svgf_amd import synth
 from tests.gbuffer_poison import poison_gbuffer
 from tests.helpers import CDT, gbuf
 
-KINDS = ("stage", "strips", "driver", "rows", "pair", "post", "stage0", "negzero", "strips2", "driver2", "wide", "widestrips", "edge", "edgedriver", "edgestrips", "graph", "fullsize", "bigstage", "motion")
-DEFAULT_KINDS = KINDS[:-2]        # (bigstage and motion run only when asked for: with them the default list would map every CLI seed to another kind)
+KINDS = ("stage", "strips", "driver", "rows", "pair", "post", "stage0", "negzero", "strips2", "driver2", "wide", "widestrips", "edge", "edgedriver", "edgestrips", "graph", "fullsize", "bigstage", "motion", "arena")
+DEFAULT_KINDS = KINDS[:-3]        # (bigstage, motion and arena run only when asked for: with them the default list would map every CLI seed to another kind)
 
 
 def _size(rng):
@@ -139,12 +140,51 @@ def _close(G, got, want, storage, what, colour_abs=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ stage vs oracle
-def trial_stage(G, oracle, seed, zeros=False, wide=False, edge=False):
+class _Placed:
+    """The device planes of one stage call of trial_stage: separate allocations, or (kind "arena") views of one caller arena with a random layout,
+    margin fill and base offsets (tests/plane_arena.py), whose margins and input planes are checked after the call."""
+
+    def __init__(self, G, ra, inputs, outputs, reach, what):
+        from svgf_amd import filter as F
+        self.F, self.what, self.ar = F, what, None
+        if ra is None:
+            self.t = {n: G.dev(a) for n, a in {**inputs, **outputs}.items()}
+            return
+        from tests import plane_arena as PA
+        planes = {**inputs, **outputs}
+        specs = [(n, a.shape, a.dtype) for n, a in planes.items()]
+        fill, tight = PA.FILLS[int(ra.integers(0, 3))], bool(ra.integers(0, 2))
+        offs = {n: int(ra.choice(PA.OFFSETS)) for n in planes}
+        self.what += f" [arena {fill}{' tight' if tight else ''} offsets {sorted(offs.values())}]"
+        self.ar = PA.Arena(specs, planes, fill=fill, tight=tight, margin_rows=reach + 8, offsets=offs, seed=int(ra.integers(0, 1 << 30)))
+        self.ar.snapshot_inputs(*inputs)
+        self.t = {n: self.ar.view(n) for n in planes}
+
+    def __getitem__(self, n):
+        return self.t[n]
+
+    def gb(self, pre=""):
+        return self.F.GBuffer(self.t[pre + "motion"], self.t[pre + "normal"], self.t.get(pre + "uv"))
+
+    def check(self):
+        if self.ar is not None:
+            import torch
+            torch.cuda.synchronize()
+            self.ar.check(self.what)
+
+
+def _gbp(f, pre=""):
+    return {pre + k: f[k] for k in ("motion", "normal", "uv")}
+
+
+def trial_stage(G, oracle, seed, zeros=False, wide=False, edge=False, arena=False):
     """zeros: -0.0, denormals and the storage type's extremes in the colour / moments planes as well (kind "stage0"; drawn from a generator of
-    their own, so that kind "stage" keeps the frames of its pinned seeds)."""
+    their own, so that kind "stage" keeps the frames of its pinned seeds).  arena: the planes of every call inside one caller arena (kind "arena";
+    its layout drawn from a generator of its own likewise)."""
     from svgf_amd import filter as F
     rng = np.random.default_rng(seed)
     rz = np.random.default_rng(seed ^ 0x5A5A5A)
+    ra = np.random.default_rng(seed ^ 0xA7E7A) if arena else None
     W, H = _size(rng)
     if wide:                                              # (kind "wide": many column tiles — the XCD-aware tile order, rows shorter than a band)
         W, H = int(rz.choice([int(rz.integers(1024, 8200)), 1920, 3840, 4096, 7680, 8191])), int(rz.integers(1, 48))
@@ -183,8 +223,11 @@ def trial_stage(G, oracle, seed, zeros=False, wide=False, edge=False):
     o = np.zeros_like(cur); hist = np.zeros((H, W), np.uint8); mom = np.zeros((H, W, 2), dt)
     oracle.temporal(W, H, storage, prev, cur, o, gbuf(f1), gbuf(f0), hist_prev, hist, mom, mom_prev, depth_threshold=tun["depth_threshold"],
                     normal_threshold=tun["normal_threshold"], history_base=tun["history_base"], mesh_id_test=tun["mesh_id_test"])
-    o_col, o_hist, o_mom = d.new_colour(), d.new_history(), d.new_moments()
-    d.TemporalFilter(G.dev(prev), G.dev(cur), o_col, G.gb_dev(f1), G.gb_dev(f0), G.dev(hist_prev), o_hist, o_mom, G.dev(mom_prev))
+    pl = _Placed(G, ra, {**_gbp(f1, "c_"), **_gbp(f0, "p_"), "prev": prev, "cur": cur, "hist_prev": hist_prev, "mom_prev": mom_prev},
+                 {"col": np.zeros_like(cur), "hist": np.zeros((H, W), np.uint8), "mom": np.zeros((H, W, 2), dt)}, 4, desc + ": temporal")
+    o_col, o_hist, o_mom = pl["col"], pl["hist"], pl["mom"]
+    d.TemporalFilter(pl["prev"], pl["cur"], o_col, pl.gb("c_"), pl.gb("p_"), pl["hist_prev"], o_hist, o_mom, pl["mom_prev"])
+    pl.check()
     try:
         assert np.array_equal(G.host(o_hist), hist), desc + ": history"
         assert _same_bits(G.host(o_col), o), desc + ": temporal colour"
@@ -205,8 +248,10 @@ def trial_stage(G, oracle, seed, zeros=False, wide=False, edge=False):
         flat[rz.integers(0, flat.size, 6)] = rz.choice(np.array([-0.0, 0.0, np.finfo(dt).tiny / 4, np.finfo(dt).tiny], np.float64), 6).astype(dt)
     want = np.zeros_like(col)
     oracle.moments(W, H, storage, col, want, momp, gbuf(fs), hl, phi_colour=tun["phi_colour"], phi_normal=tun["phi_normal"], radius=radius)
-    out = d.new_colour()
-    d.FilterMoments(G.dev(col), out, G.dev(momp), G.gb_dev(fs), G.dev(hl))
+    pl = _Placed(G, ra, {**_gbp(fs), "col": col, "momp": momp, "hl": hl}, {"out": np.zeros_like(col)}, 3, desc + ": moments")
+    out = pl["out"]
+    d.FilterMoments(pl["col"], out, pl["momp"], pl.gb(), pl["hl"])
+    pl.check()
     got = G.host(out)
     keep = hl >= 4
     assert np.array_equal(got[keep].view(np.uint8), col[keep].view(np.uint8)), desc + ": moments copy"
@@ -225,8 +270,10 @@ def trial_stage(G, oracle, seed, zeros=False, wide=False, edge=False):
         _blocks_of_negzero(rz, src, 5)
     want = np.zeros_like(src); fbw = np.full_like(src, 7)
     oracle.atrous(W, H, storage, src, want, fbw, gbuf(fs), step=step, phi_colour=tun["phi_colour"], phi_normal=tun["phi_normal"], iteration=0)
-    out, fb = d.new_colour(), G.dev(np.full_like(src, 7))
-    d.FilterKernel(G.dev(src), out, fb, G.gb_dev(fs), step, 0)
+    pl = _Placed(G, ra, {**_gbp(fs), "src": src}, {"out": np.zeros_like(src), "fb": np.full_like(src, 7)}, 2 * min(step, 64), desc + ": a-trous")
+    out, fb = pl["out"], pl["fb"]
+    d.FilterKernel(pl["src"], out, fb, pl.gb(), step, 0)
+    pl.check()
     try:
         _close(G, G.host(out), want, storage, desc + ": a-trous")
         _close(G, G.host(fb), fbw, storage, desc + ": a-trous feedback")
@@ -239,7 +286,7 @@ def trial_stage(G, oracle, seed, zeros=False, wide=False, edge=False):
         e.ctx = dict(frame=fs, src=src, got=G.host(out), want=want, step=step, denoiser=d, tun=tun)      # (for whoever re-runs the seed by hand: run_trial raises with the planes attached)
         raise
     d.close()
-    return desc + (" zeros" if zeros else "")
+    return desc + (" zeros" if zeros else "") + (" arena" if arena else "")
 
 
 # ------------------------------------------------------------------------------------------------------------------ strips vs frame driver
@@ -949,7 +996,7 @@ def trial_motion(G, oracle, seed):
     return desc
 
 
-TRIALS = {"motion": trial_motion, "bigstage": trial_bigstage, "fullsize": trial_fullsize, "graph": trial_graph, "edgestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, edge=True), "edgedriver": lambda G, oracle, seed: trial_driver(G, oracle, seed, edge=True), "edge": lambda G, oracle, seed: trial_stage(G, oracle, seed, edge=True), "wide": lambda G, oracle, seed: trial_stage(G, oracle, seed, wide=True), "widestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, wide=True),
+TRIALS = {"arena": lambda G, oracle, seed: trial_stage(G, oracle, seed, arena=True), "motion": trial_motion, "bigstage": trial_bigstage, "fullsize": trial_fullsize, "graph": trial_graph, "edgestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, edge=True), "edgedriver": lambda G, oracle, seed: trial_driver(G, oracle, seed, edge=True), "edge": lambda G, oracle, seed: trial_stage(G, oracle, seed, edge=True), "wide": lambda G, oracle, seed: trial_stage(G, oracle, seed, wide=True), "widestrips": lambda G, oracle, seed: trial_strips(G, oracle, seed, wide=True),
           "driver2": trial_driver2, "strips2": trial_strips2, "stage0": lambda G, oracle, seed: trial_stage(G, oracle, seed, zeros=True), "negzero": lambda G, oracle, seed: trial_stage(G, oracle, seed, zeros=2), "stage": trial_stage, "strips": trial_strips, "driver": trial_driver, "rows": trial_rows, "pair": trial_pair, "post": trial_post}
 
 

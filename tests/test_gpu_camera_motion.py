@@ -20,6 +20,7 @@ import pytest
 from tests import camera_scene as cs
 from tests import launch_geometry as LG
 from tests.helpers import CDT, free_running_bounds, free_running_envelope, gbuf
+from tests.plane_arena import BYTE_SENTINEL
 
 pytestmark = pytest.mark.gpu
 
@@ -348,7 +349,7 @@ def test_orbit_at_4k(G, oracle, cus):
 def _sentinel(shape, dtype):
     import torch
     t = torch.empty(shape, dtype=dtype, device="cuda")
-    t.view(torch.uint8).fill_(0xA5)
+    t.view(torch.uint8).fill_(BYTE_SENTINEL)
     return t
 
 
@@ -395,7 +396,7 @@ def test_taa_and_adapter_on_strips_and_row_ranges(G, oracle, storage):
             got = G.host(out)
             a, b = own0_ - y0, own1_ - y0
             assert np.array_equal(got[a:b].view(np.uint8), w_taa[own0_:own1_].view(np.uint8)), (y0, rows, "taa rows")
-            assert np.all(got[:a].view(np.uint8) == 0xA5) and np.all(got[b:].view(np.uint8) == 0xA5), (y0, rows, "taa wrote outside its rows")
+            assert np.all(got[:a].view(np.uint8) == BYTE_SENTINEL) and np.all(got[b:].view(np.uint8) == BYTE_SENTINEL), (y0, rows, "taa wrote outside its rows")
             want = np.zeros((rows, W, 4), dt)
             oracle.taa(W, H, storage, np.ascontiguousarray(filt[sl]), np.ascontiguousarray(hist[sl]), want, geo=(y0, rows, own0_, own1_))
             if storage == "f32":
@@ -420,7 +421,7 @@ def test_taa_and_adapter_on_strips_and_row_ranges(G, oracle, storage):
             for o, wp in zip(outs, w_pack):
                 g8 = G.host(o).view(np.uint8)
                 assert np.array_equal(g8[a:b], wp[own0_:own1_]), (y0, rows, "adapter rows")
-                assert np.all(g8[:a] == 0xA5) and np.all(g8[b:] == 0xA5), (y0, rows, "the adapter wrote outside its rows")
+                assert np.all(g8[:a] == BYTE_SENTINEL) and np.all(g8[b:] == BYTE_SENTINEL), (y0, rows, "the adapter wrote outside its rows")
             s.close()
     # row ranges of the whole-frame context (svgf_set_rows), odd first rows
     for rb, re in [(0, 1), (33, 97), (101, 102), (250, 333)]:
@@ -428,12 +429,12 @@ def test_taa_and_adapter_on_strips_and_row_ranges(G, oracle, storage):
         out = _sentinel((H, W, 4), tdt)
         whole.TAA(G.dev(filt), G.dev(hist), out)
         got = G.host(out).view(np.uint8)
-        assert np.array_equal(got[rb:re], w_taa.view(np.uint8)[rb:re]) and np.all(got[:rb] == 0xA5) and np.all(got[re:] == 0xA5), (rb, re, "taa")
+        assert np.array_equal(got[rb:re], w_taa.view(np.uint8)[rb:re]) and np.all(got[:rb] == BYTE_SENTINEL) and np.all(got[re:] == BYTE_SENTINEL), (rb, re, "taa")
         outs = [_sentinel((H, W, 4), t) for t in (torch.float32, torch.int16, torch.int16)]
         assert _pack(G, whole, fr, slice(0, H), outs) == 0
         for o, wp in zip(outs, w_pack):
             g8 = G.host(o).view(np.uint8)
-            assert np.array_equal(g8[rb:re], wp[rb:re]) and np.all(g8[:rb] == 0xA5) and np.all(g8[re:] == 0xA5), (rb, re, "adapter")
+            assert np.array_equal(g8[rb:re], wp[rb:re]) and np.all(g8[:rb] == BYTE_SENTINEL) and np.all(g8[re:] == BYTE_SENTINEL), (rb, re, "adapter")
     whole.set_rows()
     whole.close()
 

@@ -17,12 +17,12 @@ import pytest
 from svgf_amd import synth
 from tests import launch_geometry as LG
 from tests.helpers import CDT, gbuf
+from tests.plane_arena import SENTINEL, _is_sentinel, _sentinel_plane
 from tests.test_gpu_nonfinite import assert_close_with_nan, assert_same_bits_or_nan
 
 pytestmark = pytest.mark.gpu
 
 NT = min(16, int(os.environ.get("OMP_NUM_THREADS") or 8))          # oracle threads (the GPU machines give a command 16 CPUs)
-SENTINEL = {"f32": (np.uint32, 0x7FCADA55), "f16": (np.uint16, 0x7E55)}   # a quiet NaN no kernel and no input makes
 MIN_BAND = LG.constants()["kAtrousMinBand"]
 PHI_C, PHI_N = 10.0, 128.0
 PAN = (2.0, -3.0)
@@ -59,18 +59,6 @@ def frames_of():
     yield get
     _FRAMES.clear()
     gc.collect()
-
-
-def _sentinel_plane(shape, storage):
-    import torch
-    u, v = SENTINEL[storage]
-    it, ft = (torch.int32, torch.float32) if storage == "f32" else (torch.int16, torch.float16)
-    return torch.full(shape, v, dtype=it, device="cuda").view(ft)
-
-
-def _is_sentinel(a, storage):
-    u, v = SENTINEL[storage]
-    return a.view(u) == v
 
 
 def _band_of(ys, S, geo):

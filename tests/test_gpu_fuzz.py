@@ -32,7 +32,8 @@ OTHER = [("post", 213350), ("post", 215738), ("post", 320621), ("post", 400001),
          ("edgedriver", 970000), ("edgedriver", 970001), ("edgedriver", 970002), ("edgedriver", 970003),
          ("wide", 800000), ("wide", 800002), ("widestrips", 800001), ("widestrips", 800003),
          ("driver2", 700000), ("driver2", 700001), ("driver2", 700002), ("driver2", 700003), ("driver2", 700004), ("driver2", 700005),
-         ("bigstage", 1300012), ("bigstage", 1300023), ("motion", 1400000), ("motion", 1400001), ("motion", 1400007)]
+         ("bigstage", 1300012), ("bigstage", 1300023), ("motion", 1400000), ("motion", 1400001), ("motion", 1400007),
+         ("arena", 1500000), ("arena", 1500001)]
 
 
 @pytest.fixture(scope="module")
