@@ -56,19 +56,18 @@ int check_geometry(int width, int height, const svgf_strip* strip) {
     return SVGF_OK;
 }
 
-svgf::Geo geo_of(const svgf_ctx* c) { return svgf::Geo{c->W, c->H, c->strip.y0, c->strip.rows, c->rb, c->re}; }
+svgf::Geo geo_of(const svgf_ctx* c, Rows r) { return svgf::Geo{c->W, c->H, c->strip.y0, c->strip.rows, r.a, r.b}; }
+Rows rows_of(const svgf_ctx* c) { return Rows{c->rb, c->re}; }      // svgf_set_rows: what the entry points pass down
 
-// rows [rb,re) reading taps up to `reach` rows away must find them in [y0, y0+rows) or outside the frame
-int check_halo(svgf_ctx* c, int reach, const char* stage) {
-    const int lo = std::max(0, c->rb - reach), hi = std::min(c->H, c->re + reach);
-    if (c->re > c->rb && (lo < c->strip.y0 || hi > c->strip.y0 + c->strip.rows))
-        return fail(c, SVGF_ERR_HALO, std::string(stage) + ": rows need a halo of " + std::to_string(reach) + " rows that this strip does not hold");
-    return SVGF_OK;
+// rows r reading taps up to `reach` rows away must find them in [y0, y0+rows) or outside the frame
+bool halo_held(const svgf_ctx* c, Rows r, int reach) {
+    const int lo = std::max(0, r.a - reach), hi = std::min(c->H, r.b + reach);
+    return r.b <= r.a || (lo >= c->strip.y0 && hi <= c->strip.y0 + c->strip.rows);
 }
 
-bool halo_held(const svgf_ctx* c, int reach) {
-    const int lo = std::max(0, c->rb - reach), hi = std::min(c->H, c->re + reach);
-    return c->re <= c->rb || (lo >= c->strip.y0 && hi <= c->strip.y0 + c->strip.rows);
+int check_halo(svgf_ctx* c, Rows r, int reach, const char* stage) {
+    if (!halo_held(c, r, reach)) return fail(c, SVGF_ERR_HALO, std::string(stage) + ": rows need a halo of " + std::to_string(reach) + " rows that this strip does not hold");
+    return SVGF_OK;
 }
 
 int check_gbuf(svgf_ctx* c, const svgf_gbuffer* g, bool need_uv, const char* what) {
@@ -96,7 +95,7 @@ int capture_of(svgf_ctx* c, unsigned long long* id) {
 }
 
 int alloc_flags(svgf_ctx* c) {
-    if (c->young_masks && c->young_list && c->young_count && c->nan_count && c->nan_list && c->sample_count && c->estimate_host) return SVGF_OK;
+    if (c->young.complete()) return SVGF_OK;
     // (svgf_temporal_moments under stream capture, first use of a context: the allocations below would invalidate the capture and their memsets
     // would be recorded into the graph, zeroing the counters on every replay — refused like svgf_denoise_frame's first frames)
     unsigned long long cap = 0;
@@ -104,30 +103,23 @@ int alloc_flags(svgf_ctx* c) {
     if (cap) return fail(c, SVGF_ERR_INVALID, "the context's stream is being captured and this call's first use of the context allocates its scratch: enqueue one call before the capture begins");
     // all or none: the set is built aside and taken over whole, so a failed allocation leaves nothing behind that a later call would
     // mistake for a complete set
-    DevicePtr<unsigned long long> young_masks, young_count, sample_count;
-    DevicePtr<uint32_t> young_list, nan_list;
-    DevicePtr<unsigned> nan_count;
-    HostPtr<unsigned long long> estimate_host;
+    YoungScratch y;
     const size_t nmasks = (size_t)c->strip.rows * ((c->W + 63) / 64);
-    hipError_t e = acquire(young_masks, hipMalloc<unsigned long long>, nmasks * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(young_masks.get(), 0, nmasks * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = acquire(young_list, hipMalloc<uint32_t>, svgf::young_list_entries(c->strip.rows, c->W) * sizeof(uint32_t));
-    if (e == hipSuccess) e = acquire(young_count, hipMalloc<unsigned long long>, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(young_count.get(), 0, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = acquire(nan_count, hipMalloc<unsigned>, 2 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemsetAsync(nan_count.get(), 0, 2 * sizeof(unsigned), c->stream);
-    if (e == hipSuccess) e = acquire(nan_list, hipMalloc<uint32_t>, (size_t)svgf::kNanListCap * sizeof(uint32_t));
-    if (e == hipSuccess) e = acquire(sample_count, hipMalloc<unsigned long long>, 32 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(sample_count.get(), 0, 32 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = acquire(estimate_host, hipHostMalloc<unsigned long long>, 64, hipHostMallocMapped);
+    hipError_t e = acquire(y.masks, hipMalloc<unsigned long long>, nmasks * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(y.masks.get(), 0, nmasks * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = acquire(y.list, hipMalloc<uint32_t>, svgf::young_list_entries(c->strip.rows, c->W) * sizeof(uint32_t));
+    if (e == hipSuccess) e = acquire(y.count, hipMalloc<unsigned long long>, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(y.count.get(), 0, 2 * svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = acquire(y.nan_count, hipMalloc<unsigned>, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemsetAsync(y.nan_count.get(), 0, 2 * sizeof(unsigned), c->stream);
+    if (e == hipSuccess) e = acquire(y.nan_list, hipMalloc<uint32_t>, (size_t)svgf::kNanListCap * sizeof(uint32_t));
+    if (e == hipSuccess) e = acquire(y.sample_count, hipMalloc<unsigned long long>, 32 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(y.sample_count.get(), 0, 32 * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = acquire(y.estimate_host, hipHostMalloc<unsigned long long>, 64, hipHostMallocMapped);
     if (e != hipSuccess) return hip_fail(c, e, "alloc_flags");
-    *estimate_host = 0ull;
-    c->young_masks = std::move(young_masks); c->young_list = std::move(young_list); c->young_count = std::move(young_count);
-    c->nan_count = std::move(nan_count); c->nan_list = std::move(nan_list); c->sample_count = std::move(sample_count);
-    c->estimate_host = std::move(estimate_host);
+    *y.estimate_host = 0ull;
+    c->young = std::move(y);                        // (phase 0, nothing pending)
     c->dense_moments = false;
-    c->young_phase = 0;
-    c->young_pending = false;
     return SVGF_OK;
 }
 
@@ -267,7 +259,7 @@ int read_halo_violations(svgf_ctx* c, unsigned long long* count, int clear) {
     return SVGF_OK;
 }
 
-int temporal_impl(svgf_ctx* c, const void* prev_colour, const void* radiance, void* colour_out, const svgf_gbuffer* cur,
+int temporal_impl(svgf_ctx* c, Rows rows, MomentsChoice choice, const void* prev_colour, const void* radiance, void* colour_out, const svgf_gbuffer* cur,
                   const svgf_gbuffer* prev, const uint8_t* hist_prev, uint8_t* hist_cur, void* moments_cur,
                   const void* moments_prev, void* passthrough_out, int sparse_colour, void* guide_out = nullptr, const void* guide_prev = nullptr) {
     if (!prev_colour || !radiance || !colour_out || !hist_prev || !hist_cur || !moments_cur || !moments_prev)
@@ -278,59 +270,64 @@ int temporal_impl(svgf_ctx* c, const void* prev_colour, const void* radiance, vo
     if (rc != SVGF_OK) return rc;
     if (prev_colour == colour_out || hist_prev == hist_cur || moments_prev == moments_cur)
         return fail(c, SVGF_ERR_INVALID, "svgf_temporal: previous and current state planes must differ (App. B #1)");
-    if (passthrough_out && c->young_pending) {      // the lists of an earlier launch were never consumed (an error in between): start them again
-        SVGF_HIP(c, hipMemsetAsync(c->young_count.get() + c->young_phase * svgf::kYoungCounterStride, 0, svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream));
-        SVGF_HIP(c, hipMemsetAsync(c->nan_count.get() + c->young_phase, 0, sizeof(unsigned), c->stream));
+    YoungScratch& y = c->young;
+    if (passthrough_out && y.pending) {             // the lists of an earlier launch were never consumed (an error in between): start them again
+        SVGF_HIP(c, hipMemsetAsync(y.counter(), 0, svgf::kYoungCounterStride * sizeof(unsigned long long), c->stream));
+        SVGF_HIP(c, hipMemsetAsync(y.nan_counter(), 0, sizeof(unsigned), c->stream));
     }
     svgf::TemporalArgs a{prev_colour, radiance, colour_out,
                          (const float4*)cur->motion, (const uint2*)cur->normal, (const uint2*)cur->uv,
                          (const float4*)prev->motion, (const uint2*)prev->normal, (const uint2*)prev->uv,
                          hist_prev, hist_cur, moments_cur, moments_prev,
-                         c->p.depth_threshold, c->p.normal_threshold, c->p.history_base, c->p.mesh_id_test, passthrough_out,
-                         passthrough_out ? c->young_masks.get() : nullptr, passthrough_out && !c->dense_now ? c->young_list.get() : nullptr,
-                         passthrough_out ? c->young_count.get() + c->young_phase * svgf::kYoungCounterStride : nullptr,
-                         passthrough_out ? c->young_count.get() + (c->young_phase ^ 1) * svgf::kYoungCounterStride : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
-                         sparse_colour, c->p.phi_normal > 0.0f, c->halo_violations.get(),
-                         std::max(c->vy0, c->strip.y0) - c->strip.y0, std::min(c->vy1, c->strip.y0 + c->strip.rows) - c->strip.y0, (uint4*)guide_out,
-                         (const uint4*)guide_prev,
-                         c->strip.y0, c->strip.y0 + c->strip.rows,       // the guide texels of every row held (a strip runs the stage on fewer)
-                         passthrough_out ? c->nan_list.get() : nullptr, passthrough_out ? c->nan_count.get() + c->young_phase : nullptr,
-                         passthrough_out ? c->nan_count.get() + (c->young_phase ^ 1) : nullptr,
-                         passthrough_out ? c->sample_count.get() + c->young_phase * 16 : nullptr, passthrough_out ? c->sample_count.get() + (c->young_phase ^ 1) * 16 : nullptr,
-                         passthrough_out ? c->estimate_host.get() : nullptr, c->cold_now, c->p.nan_policy == SVGF_NAN_ZERO};
-    if (c->re <= c->rb) return SVGF_OK;             // nothing to launch: the young masks and the counters stay as they are
-    SVGF_HIP(c, svgf::launch_temporal(geo_of(c), c->p.storage, a, c->stream));
-    if (passthrough_out) c->young_pending = true;
+                         c->p.depth_threshold, c->p.normal_threshold, c->p.history_base, c->p.mesh_id_test, passthrough_out};
+    a.young_cap = svgf::young_append_cap(c->strip.rows, c->W);
+    a.sparse_colour = sparse_colour; a.sky_zero = c->p.phi_normal > 0.0f; a.halo_violations = c->halo_violations.get();
+    a.valid_lo = std::max(c->vy0, c->strip.y0) - c->strip.y0; a.valid_hi = std::min(c->vy1, c->strip.y0 + c->strip.rows) - c->strip.y0;
+    a.guide_out = (uint4*)guide_out; a.guide_prev = (const uint4*)guide_prev;
+    a.guide_lo = c->strip.y0; a.guide_hi = c->strip.y0 + c->strip.rows;      // the guide texels of every row held (a strip runs the stage on fewer)
+    a.sample_off = choice.cold; a.heal_nan = c->p.nan_policy == SVGF_NAN_ZERO;
+    if (passthrough_out) {                          // frame / strip drivers, svgf_temporal_moments: the scratch the moments launch of this frame reads
+        a.young_masks = y.masks.get(); a.young_list = choice.dense() ? nullptr : y.list.get();
+        a.young_count = y.counter(); a.young_count_next = y.counter(true);
+        a.nan_list = y.nan_list.get(); a.nan_count = y.nan_counter(); a.nan_count_next = y.nan_counter(true);
+        a.sample_count = y.sample_counter(); a.sample_prev = y.sample_counter(true); a.estimate_host = y.estimate_host.get();
+    }
+    if (rows.b <= rows.a) return SVGF_OK;           // nothing to launch: the young masks and the counters stay as they are
+    SVGF_HIP(c, svgf::launch_temporal(geo_of(c, rows), c->p.storage, a, c->stream));
+    if (passthrough_out) y.pending = true;
     return SVGF_OK;
 }
 
-int moments_impl(svgf_ctx* c, const void* colour, void* out, const void* moments, const svgf_gbuffer* g, const uint8_t* hist, int cold_only,
-                 int dense, int sparse_colour) {
+// cold_only: behind a temporal launch that wrote passthrough_out, on the kernel `choice` names.  Else (svgf_moments) every pixel is visited: the LDS-streaming kernel (variant
+// DIRECT, a radius other than 3 or PhiNormal == 0: the per-pixel one); the young-pixel launch evaluates its taps as whichever of the two that call runs (moments_group8): same bits.
+int moments_impl(svgf_ctx* c, Rows rows, MomentsChoice choice, const void* colour, void* out, const void* moments, const svgf_gbuffer* g, const uint8_t* hist,
+                 int cold_only, int sparse_colour) {
     if (!colour || !out || !moments || !hist) return fail(c, SVGF_ERR_INVALID, "svgf_moments: null plane");
     if (colour == out) return fail(c, SVGF_ERR_INVALID, "svgf_moments: in-place filtering is a race");
     int rc = check_gbuf(c, g, false, "svgf_moments");
-    if (rc == SVGF_OK) rc = check_halo(c, c->p.moments_radius, "svgf_moments");
+    if (rc == SVGF_OK) rc = check_halo(c, rows, c->p.moments_radius, "svgf_moments");
     if (rc != SVGF_OK) return rc;
+    YoungScratch& y = c->young;
+    const int dense = cold_only ? choice.dense() : c->p.variant != SVGF_VARIANT_DIRECT;
     svgf::MomentsArgs a{colour, out, moments, (const float4*)g->motion, (const uint2*)g->normal, hist,
                         c->p.phi_colour, c->p.phi_normal, c->p.moments_radius, cold_only, dense, sparse_colour,
-                        cold_only ? c->young_masks.get() : nullptr, cold_only ? c->young_list.get() : nullptr, cold_only ? c->young_count.get() + c->young_phase * svgf::kYoungCounterStride : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
-                        cold_only ? c->nan_list.get() : nullptr, cold_only ? c->nan_count.get() + c->young_phase : nullptr,
+                        cold_only ? y.masks.get() : nullptr, cold_only ? y.list.get() : nullptr, cold_only ? y.counter() : nullptr, svgf::young_append_cap(c->strip.rows, c->W),
+                        cold_only ? y.nan_list.get() : nullptr, cold_only ? y.nan_counter() : nullptr,
                         c->p.variant == SVGF_VARIANT_LDS_GENERAL};
-    if (c->re <= c->rb) {
-        // No moments rows.  If the temporal launch of this frame did run (young_pending), its list is dropped: the counter pair still
+    if (rows.b <= rows.a) {
+        // No moments rows.  If the temporal launch of this frame did run (pending), its list is dropped: the counter pair still
         // has to turn over, because that launch zeroed the OTHER counter for the next frame.
-        if (cold_only && c->young_pending) { c->young_phase ^= 1; c->young_pending = false; }
+        if (cold_only && y.pending) y.turn();
         return SVGF_OK;
     }
-    SVGF_HIP(c, svgf::launch_moments(geo_of(c), c->p.storage, a, c->p.variant == SVGF_VARIANT_DIRECT, c->stream));
-    if (cold_only) { c->young_phase ^= 1; c->young_pending = false; }   // the next frame's temporal launch appends to the counter this frame's one zeroed
+    SVGF_HIP(c, svgf::launch_moments(geo_of(c, rows), c->p.storage, a, c->p.variant == SVGF_VARIANT_DIRECT, c->stream));
+    if (cold_only) y.turn();
     return SVGF_OK;
 }
 
 bool use_guide(const svgf_ctx* c) {
     return (c->p.storage == SVGF_F32 || SVGF_GUIDE_F16) && c->p.steps >= SVGF_GUIDE_MIN_STEPS && c->p.variant != SVGF_VARIANT_DIRECT && c->guide != nullptr;
 }
-
 
 // The reprojection test reads {depth, normal, instance ID} of the previous G-buffer; the guide plane the previous frame wrote
 // holds exactly those bits.  It stands in for `prev` only when `prev` IS the G-buffer that frame was given as current (same
@@ -363,53 +360,56 @@ static unsigned long long* path_stats_of(const svgf_ctx* c, int step) {
     return i < SVGF_PATH_STAT_STEPS ? c->path_stats.get() + 2 * i : nullptr;
 }
 
-int atrous_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide) {
-    if (!in || !out) return fail(c, SVGF_ERR_INVALID, "svgf_atrous: null plane");
-    if (in == out || in == feedback) return fail(c, SVGF_ERR_INVALID, "svgf_atrous: in-place filtering is a race");
-    if (step < 1 || step > (1 << SVGF_MAX_STEPS)) return fail(c, SVGF_ERR_INVALID, "svgf_atrous: step out of range");
-    int rc = check_gbuf(c, g, false, "svgf_atrous");
-    if (rc == SVGF_OK) rc = check_halo(c, 2 * step, "svgf_atrous");
+// The argument block of an a-trous launch of this context, and the checks its three forms share (`pair`: iterations 0 and 1 in one launch, which
+// always feeds back and counts no paths).  The halo is the caller's to check: it knows its rows.
+svgf::AtrousArgs atrous_args(const svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, const void* guide) {
+    return svgf::AtrousArgs{in, out, feedback, g ? (const float4*)g->motion : nullptr, g ? (const uint2*)g->normal : nullptr,
+                            step, c->p.phi_colour, c->p.phi_normal, (const uint4*)guide, c->p.variant == SVGF_VARIANT_LDS_GENERAL, path_stats_of(c, step)};
+}
+int atrous_checked(svgf_ctx* c, bool pair, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide, svgf::AtrousArgs* a) {
+    const std::string name = pair ? "svgf_atrous_pair" : "svgf_atrous";
+    if (!in || !out) return fail(c, SVGF_ERR_INVALID, name + ": null plane");
+    if (in == out || in == feedback || (pair && out == feedback))
+        return fail(c, SVGF_ERR_INVALID, name + (pair ? ": in, out and feedback must be three planes" : ": in-place filtering is a race"));
+    if (step < 1 || step > (1 << SVGF_MAX_STEPS)) return fail(c, SVGF_ERR_INVALID, name + ": step out of range");
+    if (int rc = check_gbuf(c, g, false, name.c_str()); rc != SVGF_OK) return rc;
+    *a = atrous_args(c, in, out, iteration == 0 ? feedback : nullptr, g, step, guide);
+    if (pair) a->path_stats = nullptr;
+    return SVGF_OK;
+}
+
+int atrous_impl(svgf_ctx* c, Rows rows, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide) {
+    svgf::AtrousArgs a;
+    int rc = atrous_checked(c, false, in, out, feedback, g, step, iteration, guide, &a);
+    if (rc == SVGF_OK) rc = check_halo(c, rows, 2 * step, "svgf_atrous");
     if (rc != SVGF_OK) return rc;
-    svgf::AtrousArgs a{in, out, iteration == 0 ? feedback : nullptr, (const float4*)g->motion, (const uint2*)g->normal,
-                       step, c->p.phi_colour, c->p.phi_normal, (const uint4*)guide, c->p.variant == SVGF_VARIANT_LDS_GENERAL, path_stats_of(c, step)};
-    SVGF_HIP(c, svgf::launch_atrous(geo_of(c), c->p.storage, c->p.variant, a, c->stream));
+    SVGF_HIP(c, svgf::launch_atrous(geo_of(c, rows), c->p.storage, c->p.variant, a, c->stream));
     return SVGF_OK;
 }
 
 // One iteration over up to three row ranges in ONE launch, the first `nfirst` ranges produced first and signalled (svgf_kernels.h: AtrousRanges;
 // the strip driver's edge rows, svgf_strip.hip).  The caller has checked atrous_ranges_ok().
 bool atrous_ranges_ok(const svgf_ctx* c, int step) {
-    svgf::AtrousArgs a{};
-    a.step = step; a.phi_normal = c->p.phi_normal;
-    return svgf::atrous_ranges_available(c->p.variant, a);
+    return svgf::atrous_ranges_available(c->p.variant, atrous_args(c, nullptr, nullptr, nullptr, nullptr, step, nullptr));
 }
-int atrous_ranges_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide, const svgf::AtrousRanges& r) {
-    if (!in || !out) return fail(c, SVGF_ERR_INVALID, "svgf_atrous: null plane");
-    if (in == out || in == feedback) return fail(c, SVGF_ERR_INVALID, "svgf_atrous: in-place filtering is a race");
-    int rc = check_gbuf(c, g, false, "svgf_atrous");
+int atrous_ranges_impl(svgf_ctx* c, Rows hull, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide, const svgf::AtrousRanges& r) {
+    svgf::AtrousArgs a;
+    int rc = atrous_checked(c, false, in, out, feedback, g, step, iteration, guide, &a);
+    for (int k = 0; k < r.n && rc == SVGF_OK; k++) rc = check_halo(c, Rows{r.yb[k], r.ye[k]}, 2 * step, "svgf_atrous");
     if (rc != SVGF_OK) return rc;
-    const int rb = c->rb, re = c->re;
-    for (int k = 0; k < r.n && rc == SVGF_OK; k++) { c->rb = r.yb[k]; c->re = r.ye[k]; rc = check_halo(c, 2 * step, "svgf_atrous"); }
-    c->rb = rb; c->re = re;
-    if (rc != SVGF_OK) return rc;
-    svgf::AtrousArgs a{in, out, iteration == 0 ? feedback : nullptr, (const float4*)g->motion, (const uint2*)g->normal,
-                       step, c->p.phi_colour, c->p.phi_normal, (const uint4*)guide, c->p.variant == SVGF_VARIANT_LDS_GENERAL, path_stats_of(c, step)};
-    SVGF_HIP(c, svgf::launch_atrous_ranges(geo_of(c), c->p.storage, a, r, c->stream));
+    SVGF_HIP(c, svgf::launch_atrous_ranges(geo_of(c, hull), c->p.storage, a, r, c->stream));
     return SVGF_OK;
 }
 
 // Iterations 0 and 1 of application::WaveletFilter's loop (App.cu:497-507: steps 1 and 2) as ONE launch: iteration 0's rows never
-// leave the chip except as the feedback plane (svgf_atrous_fused.h).  `out` receives iteration 1's result on rows [rb, re).
-int atrous_pair_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, const void* guide) {
-    if (!in || !out) return fail(c, SVGF_ERR_INVALID, "svgf_atrous_pair: null plane");
-    if (in == out || in == feedback || out == feedback) return fail(c, SVGF_ERR_INVALID, "svgf_atrous_pair: in, out and feedback must be three planes");
-    int rc = check_gbuf(c, g, false, "svgf_atrous_pair");
-    if (rc == SVGF_OK) rc = check_halo(c, 2 + 4 + 0, "svgf_atrous_pair");       // iteration 1 reaches 4 rows of iteration 0, which reaches 2
+// leave the chip except as the feedback plane (svgf_atrous_fused.h).  `out` receives iteration 1's result on `rows`.
+int atrous_pair_impl(svgf_ctx* c, Rows rows, const void* in, void* out, void* feedback, const svgf_gbuffer* g, const void* guide) {
+    svgf::AtrousArgs a;
+    int rc = atrous_checked(c, true, in, out, feedback, g, 1, 0, guide, &a);
+    if (rc == SVGF_OK) rc = check_halo(c, rows, 2 + 4 + 0, "svgf_atrous_pair");       // iteration 1 reaches 4 rows of iteration 0, which reaches 2
     if (rc != SVGF_OK) return rc;
-    svgf::AtrousArgs a{in, out, feedback, (const float4*)g->motion, (const uint2*)g->normal,
-                       1, c->p.phi_colour, c->p.phi_normal, (const uint4*)guide, c->p.variant == SVGF_VARIANT_LDS_GENERAL};
     if (!svgf::atrous_fused_available(c->p.variant, a)) return fail(c, SVGF_ERR_INVALID, "svgf_atrous_pair: needs the LDS kernels (variant != direct) and PhiNormal != 0");
-    SVGF_HIP(c, svgf::launch_atrous_fused(geo_of(c), c->p.storage, a, c->stream));
+    SVGF_HIP(c, svgf::launch_atrous_fused(geo_of(c, rows), c->p.storage, a, c->stream));
     return SVGF_OK;
 }
 
@@ -424,41 +424,34 @@ bool can_fuse01(const svgf_ctx* c) {
 // (fast camera motion, a cut without a reset; back below 5 %) or that more waves hold young pixels than the list takes appends from (thin geometry
 // under motion; back below three quarters of that: the bench pan's 8 000 - 10 000 such waves must not keep a context there).  Both kernels evaluate
 // the estimate on the same bits (moments_group8, ARITH = 1), so the choice — and the timing it depends on — changes nothing but the frame time; the
-// ranks of a strip driver choose each for itself.  Rows: [c->rb, c->re) as they are when this is called (the temporal rows).
-void choose_moments_kernel(svgf_ctx* c, bool* cold, bool* crowded) {
+// ranks of a strip driver choose each for itself.  rt: the rows of the frame's temporal launch, which the sample is an estimate over.
+MomentsChoice choose_moments_kernel(svgf_ctx* c, Rows rt) {
     // Only where launch_moments has a kernel that visits every pixel for a dense frame: the LDS-streaming one (the reference's radius, PhiNormal != 0)
     // or the 3x3 shuffle kernel.  Any other setting keeps the young-pixel launch — which needs the temporal launch's LIST, and a cold or crowded
     // frame's temporal launch appends to none (radius 0 / 2 or PhiNormal == 0 under the default variants lost the young pixels of the
     // partly young segments of the first three frames).
     const bool streams = c->p.variant != SVGF_VARIANT_DIRECT && ((c->p.moments_radius == 3 && c->p.phi_normal != 0.0f) || c->p.moments_radius == 1);
-    *cold = c->frames_since_reset < 3 && streams;
-    *crowded = false;
-    if (!*cold && c->adaptive_moments && c->estimate_host && streams && c->p.moments_radius == 3 && c->re > c->rb) {
-        const unsigned long long sample = *(volatile unsigned long long*)c->estimate_host.get();   // {waves that hold some young pixels: high word, young pixels: low word}, of one wave in 64
-        const double est = 64.0 * (double)(unsigned)sample / ((double)c->W * (double)(c->re - c->rb));
+    MomentsChoice choice;
+    choice.cold = c->frames_since_reset < 3 && streams;
+    if (!choice.cold && c->adaptive_moments && c->young.estimate_host && streams && c->p.moments_radius == 3 && rt.b > rt.a) {
+        const unsigned long long sample = *(volatile unsigned long long*)c->young.estimate_host.get();   // {waves that hold some young pixels: high word, young pixels: low word}, of one wave in 64
+        const double est = 64.0 * (double)(unsigned)sample / ((double)c->W * (double)(rt.b - rt.a));
         const unsigned long long appends = 64ull * (sample >> 32), cap = svgf::young_append_cap(c->strip.rows, c->W);   // what the list of such a frame takes, and its cap
         if (est > 0.08 || appends > cap) c->dense_moments = true;
         else if (est < 0.05 && appends < cap / 4 * 3) c->dense_moments = false;
-        *crowded = c->dense_moments;
+        choice.crowded = c->dense_moments;
     }
-    c->dense_now = *cold || *crowded;               // (the temporal launch of such a frame appends to no list)
-    c->cold_now = *cold;                            // (... and of a cold one adds nothing to the sample)
+    return choice;
 }
 
-int temporal_moments_impl(svgf_ctx* c, const void* prev_colour, const void* radiance, void* colour_out, void* filter_out,
-                          const svgf_gbuffer* cur, const svgf_gbuffer* prev, const uint8_t* hist_prev, uint8_t* hist_cur,
-                          void* moments_cur, const void* moments_prev, int mrb, int mre, int feedback_follows, void* guide_out, const void* guide_prev, int dense) {
+int temporal_moments_impl(svgf_ctx* c, Rows rt, Rows rm, MomentsChoice choice, const void* prev_colour, const void* radiance, void* colour_out,
+                          void* filter_out, const svgf_gbuffer* cur, const svgf_gbuffer* prev, const uint8_t* hist_prev, uint8_t* hist_cur,
+                          void* moments_cur, const void* moments_prev, int feedback_follows, void* guide_out, const void* guide_prev) {
     if (!filter_out || filter_out == colour_out) return fail(c, SVGF_ERR_INVALID, "svgf_temporal_moments: filter_out must be a plane of its own");
-    const int rb = c->rb, re = c->re;
-    if (mrb == -1 && mre == -1) { mrb = rb; mre = re; }
-    if (mrb < rb || mre > re || mrb > mre) return fail(c, SVGF_ERR_INVALID, "svgf_temporal_moments: moments rows outside the temporal rows");
+    if (rm.a < rt.a || rm.b > rt.b || rm.a > rm.b) return fail(c, SVGF_ERR_INVALID, "svgf_temporal_moments: moments rows outside the temporal rows");
     int rc = alloc_flags(c);
-    if (rc == SVGF_OK) rc = temporal_impl(c, prev_colour, radiance, colour_out, cur, prev, hist_prev, hist_cur, moments_cur, moments_prev, filter_out, feedback_follows != 0, guide_out, guide_prev);
-    c->dense_now = c->cold_now = false;             // (a driver's choice for THIS frame, choose_moments_kernel: the stage calls keep their lists)
-    if (rc != SVGF_OK) return rc;
-    c->rb = mrb; c->re = mre;
-    rc = moments_impl(c, colour_out, filter_out, moments_cur, cur, hist_cur, 1, dense, feedback_follows != 0);
-    c->rb = rb; c->re = re;
+    if (rc == SVGF_OK) rc = temporal_impl(c, rt, choice, prev_colour, radiance, colour_out, cur, prev, hist_prev, hist_cur, moments_cur, moments_prev, filter_out, feedback_follows != 0, guide_out, guide_prev);
+    if (rc == SVGF_OK) rc = moments_impl(c, rm, choice, colour_out, filter_out, moments_cur, cur, hist_cur, 1, feedback_follows != 0);
     return rc;
 }
 
@@ -548,8 +541,7 @@ int svgf_resize_strip(svgf_ctx* c, int width, int height, const svgf_strip* stri
     c->in_flight = false;
     for (int i = 0; i < 2; i++) { c->colour[i].reset(); c->moments[i].reset(); c->filter[i].reset(); c->hist[i].reset(); c->filter_alt[i].reset(); }
     c->guide.reset(); c->guide_prev.reset();
-    c->young_masks.reset(); c->young_list.reset(); c->young_count.reset(); c->nan_count.reset(); c->nan_list.reset(); c->sample_count.reset();
-    c->estimate_host.reset(); c->halo_violations.reset();
+    c->young.reset(); c->halo_violations.reset();
     c->have_state = false; c->guide_prev_valid = false;
     c->W = width; c->H = height; c->strip = *strip; c->rb = strip->own_begin; c->re = strip->own_end;
     c->vy0 = strip->y0; c->vy1 = strip->y0 + strip->rows;
@@ -622,8 +614,8 @@ int svgf_set_adaptive_moments(svgf_ctx* c, int enable) {
 int svgf_adaptive_moments_state(const svgf_ctx* c) { return c && c->dense_moments ? 1 : 0; }
 
 int svgf_adaptive_moments_sample(const svgf_ctx* c, unsigned* young_pixels, unsigned* appending_waves) {
-    if (!c || !c->estimate_host) return SVGF_ERR_INVALID;
-    const unsigned long long sample = *(volatile unsigned long long*)c->estimate_host.get();
+    if (!c || !c->young.estimate_host) return SVGF_ERR_INVALID;
+    const unsigned long long sample = *(volatile unsigned long long*)c->young.estimate_host.get();
     auto sat = [](unsigned long long v) { return v > 0xffffffffull ? 0xffffffffu : (unsigned)v; };
     if (young_pixels) *young_pixels = sat(64ull * (sample & 0xffffffffull));
     if (appending_waves) *appending_waves = sat(64ull * (sample >> 32));
@@ -641,15 +633,13 @@ int svgf_temporal(svgf_ctx* c, const void* prev_colour, const void* radiance, vo
                   const void* moments_prev) {
     if (!c) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
-    return temporal_impl(c, prev_colour, radiance, colour_out, cur, prev, hist_prev, hist_cur, moments_cur, moments_prev, nullptr, 0);
+    return temporal_impl(c, rows_of(c), MomentsChoice{}, prev_colour, radiance, colour_out, cur, prev, hist_prev, hist_cur, moments_cur, moments_prev, nullptr, 0);
 }
 
 int svgf_moments(svgf_ctx* c, const void* colour, void* out, const void* moments, const svgf_gbuffer* g, const uint8_t* hist) {
     if (!c) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
-    // stage call: every pixel is visited — the LDS-streaming kernel (variant DIRECT, a radius other than 3 or PhiNormal == 0: the per-pixel one).
-    // The frame driver's young-pixel launch evaluates its taps as whichever of the two this call runs does (moments_group8): bit-identical results.
-    return moments_impl(c, colour, out, moments, g, hist, 0, c->p.variant != SVGF_VARIANT_DIRECT, 0);
+    return moments_impl(c, rows_of(c), MomentsChoice{}, colour, out, moments, g, hist, 0, 0);      // stage call: every pixel is visited
 }
 
 int svgf_temporal_moments(svgf_ctx* c, const void* prev_colour, const void* radiance, void* colour_out, void* filter_out,
@@ -657,19 +647,20 @@ int svgf_temporal_moments(svgf_ctx* c, const void* prev_colour, const void* radi
                           void* moments_cur, const void* moments_prev, int mrb, int mre, int feedback_follows) {
     if (!c) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
-    return temporal_moments_impl(c, prev_colour, radiance, colour_out, filter_out, cur, prev, hist_prev, hist_cur, moments_cur, moments_prev, mrb, mre, feedback_follows);
+    const Rows rt = rows_of(c), rm = mrb == -1 && mre == -1 ? rt : Rows{mrb, mre};
+    return temporal_moments_impl(c, rt, rm, MomentsChoice{}, prev_colour, radiance, colour_out, filter_out, cur, prev, hist_prev, hist_cur, moments_cur, moments_prev, feedback_follows);
 }
 
 int svgf_atrous(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration) {
     if (!c) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
-    return atrous_impl(c, in, out, feedback, g, step, iteration);
+    return atrous_impl(c, rows_of(c), in, out, feedback, g, step, iteration);
 }
 
 int svgf_atrous_pair(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g) {
     if (!c) return SVGF_ERR_INVALID;
     DeviceGuard dg(c->device);
-    return atrous_pair_impl(c, in, out, feedback, g);
+    return atrous_pair_impl(c, rows_of(c), in, out, feedback, g);
 }
 
 int svgf_set_iteration_fusion(svgf_ctx* c, int enable) {
@@ -698,10 +689,10 @@ int svgf_taa(svgf_ctx* c, const void* filtered, const void* history, void* out) 
     if (!c) return SVGF_ERR_INVALID;
     if (!filtered || !history || !out) return fail(c, SVGF_ERR_INVALID, "svgf_taa: null plane");
     if (out == filtered || out == history) return fail(c, SVGF_ERR_INVALID, "svgf_taa: in-place filtering is a race");
-    int rc = check_halo(c, 3, "svgf_taa");                                // samples sit 1-3 texels up-left of the pixel (fp32 rounding of uv*(N-1))
+    int rc = check_halo(c, rows_of(c), 3, "svgf_taa");                                // samples sit 1-3 texels up-left of the pixel (fp32 rounding of uv*(N-1))
     if (rc != SVGF_OK) return rc;
     DeviceGuard dg(c->device);
-    SVGF_HIP(c, svgf::launch_taa(geo_of(c), c->p.storage, filtered, history, out, c->p.variant == SVGF_VARIANT_DIRECT, c->stream));
+    SVGF_HIP(c, svgf::launch_taa(geo_of(c, rows_of(c)), c->p.storage, filtered, history, out, c->p.variant == SVGF_VARIANT_DIRECT, c->stream));
     return SVGF_OK;
 }
 
@@ -710,7 +701,7 @@ static int albedo_impl(svgf_ctx* c, int mode, const void* in, const void* albedo
     if (!in || !albedo || !out) return fail(c, SVGF_ERR_INVALID, std::string(what) + ": null plane");
     if (albedo == out) return fail(c, SVGF_ERR_INVALID, std::string(what) + ": out must not alias the albedo plane");
     DeviceGuard dg(c->device);
-    SVGF_HIP(c, svgf::launch_albedo(geo_of(c), c->p.storage, mode, in, albedo, out, c->stream));
+    SVGF_HIP(c, svgf::launch_albedo(geo_of(c, rows_of(c)), c->p.storage, mode, in, albedo, out, c->stream));
     return SVGF_OK;
 }
 int svgf_demodulate(svgf_ctx* c, const void* radiance, const void* albedo, void* out) { return albedo_impl(c, 0, radiance, albedo, out, "svgf_demodulate"); }
@@ -720,14 +711,14 @@ int svgf_pack_gbuffer(svgf_ctx* c, const void* position, const void* normal, con
                       void* motion_out, void* normal_out, void* uv_out) {
     if (!c) return SVGF_ERR_INVALID;
     if (!position || !normal || !bary || !cam || !motion_out || !normal_out || !uv_out) return fail(c, SVGF_ERR_INVALID, "svgf_pack_gbuffer: null argument");
-    int rc = check_halo(c, 1, "svgf_pack_gbuffer");                       // the 2x2 quad partner row
+    int rc = check_halo(c, rows_of(c), 1, "svgf_pack_gbuffer");                       // the 2x2 quad partner row
     if (rc != SVGF_OK) return rc;
     svgf::PackArgs a;
     a.position = (const float4*)position; a.normal = (const float4*)normal; a.bary = (const float4*)bary;
     std::memcpy(a.vp, cam->view_proj, sizeof(a.vp)); std::memcpy(a.pvp, cam->prev_view_proj, sizeof(a.pvp)); std::memcpy(a.cam, cam->position, sizeof(a.cam));
     a.motion = (float4*)motion_out; a.normal_out = (uint2*)normal_out; a.uv_out = (uint2*)uv_out;
     DeviceGuard dg(c->device);
-    SVGF_HIP(c, svgf::launch_pack_gbuffer(geo_of(c), a, c->stream));
+    SVGF_HIP(c, svgf::launch_pack_gbuffer(geo_of(c, rows_of(c)), a, c->stream));
     return SVGF_OK;
 }
 
@@ -785,7 +776,7 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     rc = capture_of(c, &cap);
     if (rc != SVGF_OK) return rc;
     if (cap) {
-        const bool allocates = !c->have_state || !(c->young_masks && c->young_list && c->young_count && c->nan_count && c->nan_list && c->sample_count && c->estimate_host) ||
+        const bool allocates = !c->have_state || !c->young.complete() ||
                                (c->frames_in_flight > 1 && !(c->filter_alt[0] && c->filter_alt[1])) || (is_strip(c) && !c->halo_violations);
         if (allocates || c->frames_since_reset < 3)
             return fail(c, SVGF_ERR_INVALID, "svgf_denoise_frame: the context's stream is being captured and this frame cannot be: the first three frames after "
@@ -797,6 +788,7 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     rc = begin_frame(c);                            // (frames in flight: the previous frame's result sits in the other pair until the call after this)
     if (rc != SVGF_OK) return rc;
     const int P = c->pingpong;
+    const Rows rows = rows_of(c);
 
     svgf_ctx::FrameEvents fe;
     const bool timed = !cap && c->timing > 0 && (c->timing_phase++ % c->timing) == 0;     // (events of a captured frame are graph nodes: nothing to read back)
@@ -818,14 +810,14 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         // SVGFDebugOutput::TemporalFilter (App.cu:602-609): the temporal stage alone, its result is the frame.
         // SVGFDebugOutput::ATrousWaveletFilter / Depth (App.cu:611-620, 632-638): temporal, then the wavelet filter WITHOUT
         // FilterMoments — FilterBuffer[0] still holds the previous frame's result (App. B #11), which is what gets filtered.
-        rc = temporal_impl(c, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(), c->moments[P].get(), c->moments[1 - P].get(), nullptr, 0);
+        rc = temporal_impl(c, rows, MomentsChoice{}, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(), c->moments[P].get(), c->moments[1 - P].get(), nullptr, 0);
         if (rc != SVGF_OK) return bail(rc);
         stamp(); stamp();
         const void* res = c->colour[P].get();
         int pp = c->result_index;
         if (c->debug_mode == SVGF_DEBUG_ATROUS) {
             for (int i = 0; i < c->p.steps; i++) {
-                rc = atrous_impl(c, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i);
+                rc = atrous_impl(c, rows, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i);
                 if (rc != SVGF_OK) return bail(rc);
                 stamp();
                 pp ^= 1;
@@ -842,10 +834,9 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     }
     // With at least one wavelet iteration the temporal result in colour[P] is dead where iteration 0's feedback will
     // overwrite it (:619-622): it is only stored for young pixels (the moments estimate reads them) and depth-0 texels.
-    bool cold = false, crowded = false;
-    choose_moments_kernel(c, &cold, &crowded);
+    const MomentsChoice choice = choose_moments_kernel(c, rows);
     // (a crowded frame keeps every pixel's temporal colour: the streaming kernel reads its taps from one plane)
-    const int sparse = c->p.steps >= 1 && !crowded;
+    const int sparse = c->p.steps >= 1 && !choice.crowded;
     // The temporal launch also writes the filter buffer where history >= 4 (there FilterMoments is a copy), the
     // moments launch then only works on young pixels: same planes, 32 B/px less traffic in steady state.
     // ... and repacks what the wavelet iterations read of the G-buffer ({depth, ddepth, normal}: 16 B instead of 24 B of lines per
@@ -855,13 +846,12 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     // ... and the NEXT frame's reprojection test reads this frame's guide plane instead of the three planes of its previous
     // G-buffer (prev_guide_for): -16 B/px of the temporal launch's 146
     void* guide = use_guide(c) ? c->guide.get() : nullptr;
-    rc = temporal_impl(c, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(),
+    rc = temporal_impl(c, rows, choice, c->colour[1 - P].get(), radiance, c->colour[P].get(), cur, prev, c->hist[1 - P].get(), c->hist[P].get(),
                        c->moments[P].get(), c->moments[1 - P].get(), c->filter[0].get(), sparse, guide, prev_guide_for(c, cur, prev));  // App.cu:552
-    c->dense_now = c->cold_now = false;             // (the stage calls on this context keep their lists)
     if (rc != SVGF_OK) return bail(rc);
     stamp();
     // the first three frames after a reset have history <= 3 everywhere: the LDS-streaming moments kernel
-    rc = moments_impl(c, c->colour[P].get(), c->filter[0].get(), c->moments[P].get(), cur, c->hist[P].get(), 1, cold || crowded, sparse);   // App.cu:554 (current moments: App. B #4)
+    rc = moments_impl(c, rows, choice, c->colour[P].get(), c->filter[0].get(), c->moments[P].get(), cur, c->hist[P].get(), 1, sparse);   // App.cu:554 (current moments: App. B #4)
     if (rc != SVGF_OK) return bail(rc);
     stamp();
     int pp = 0, first = 0;
@@ -869,13 +859,13 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
     // The pair launch stores iteration 0's feedback on [rb - 4, re + 4) inside the frame: with svgf_set_rows narrower than the frame those
     // rows lie outside what this frame's temporal launch wrote, and feedback computed from last frame's filter plane would replace
     // colour rows the two-launch sequence leaves alone.  So: only on the whole frame.
-    const bool pair = can_fuse01(c) && halo_held(c, 6) && c->rb == 0 && c->re == c->H;
+    const bool pair = can_fuse01(c) && halo_held(c, rows, 6) && rows.a == 0 && rows.b == c->H;
     if (pair) {
         // iterations 0 and 1 as one launch: c->filter[0] -> c->filter[1] (iteration 0's own plane is never written), feedback as ever
-        rc = atrous_pair_impl(c, c->filter[0].get(), c->filter[1].get(), c->colour[P].get(), cur, guide);
+        rc = atrous_pair_impl(c, rows, c->filter[0].get(), c->filter[1].get(), c->colour[P].get(), cur, guide);
         if (rc == SVGF_OK) { stamp(); stamp(); pp = 1; first = 2; }             // timing slot 2 holds the pair, slot 3 (next to) nothing
     } else if (c->p.steps >= 1) {
-        rc = atrous_impl(c, c->filter[0].get(), c->filter[1].get(), c->colour[P].get(), cur, 1, 0, guide);        // App.cu:497-507, iteration 0: feeds the history back
+        rc = atrous_impl(c, rows, c->filter[0].get(), c->filter[1].get(), c->colour[P].get(), cur, 1, 0, guide);        // App.cu:497-507, iteration 0: feeds the history back
         if (rc == SVGF_OK) { stamp(); pp = 1; first = 1; }
     }
     // With two frames in flight the remaining iterations leave the caller's stream (tail_may_leave).  (Iteration 0 on the side stream as well -
@@ -891,7 +881,7 @@ int svgf_denoise_frame(svgf_ctx* c, const void* radiance, const svgf_gbuffer* cu
         } else rc = join_side(c, caller_stream);
     }
     for (int i = first; i < c->p.steps && rc == SVGF_OK; i++) {
-        rc = atrous_impl(c, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i, guide);
+        rc = atrous_impl(c, rows, c->filter[pp].get(), c->filter[1 - pp].get(), c->colour[P].get(), cur, 1 << i, i, guide);
         if (rc == SVGF_OK) { stamp(); pp ^= 1; }
     }
     if (aside) {

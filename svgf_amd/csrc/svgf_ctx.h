@@ -35,6 +35,35 @@ template <class H, class F, class... A> hipError_t acquire(H& h, F make, A... ar
     return e;
 }
 
+struct Rows { int a, b; };              // global rows [a, b): what ONE launch computes — an argument of every stage helper, never context state
+
+// Which kernel serves a frame's young pixels: the drivers' decision for one frame (choose_moments_kernel), handed to that frame's temporal and
+// moments launches.  The stage entry points pass the default: their temporal launch appends to the list and adds to the sample.
+struct MomentsChoice {
+    bool cold = false, crowded = false;     // one of the first three frames after a reset; the sample says too many young pixels for the list
+    bool dense() const { return cold || crowded; }   // the streaming kernel visits every pixel: the temporal launch appends to no list
+};
+
+// Scratch a temporal launch hands to the moments launch of the same frame (TemporalArgs / MomentsArgs, svgf_kernels.h).  All of it or none
+// (alloc_flags).  The three device counters are pairs used in turn: a frame's temporal launch appends to the current one and zeroes the next.
+struct YoungScratch {
+    DevicePtr<unsigned long long> masks;   // per (row, 64-column segment) the lanes whose pixel (history < 4) needs the spatial estimate
+    DevicePtr<uint32_t> list;              // the indices of the pixels of the partly young segments (svgf::young_list_entries)
+    DevicePtr<unsigned long long> count;   // {appends, pixels} counters of `list`, svgf::kYoungCounterStride words apart
+    DevicePtr<uint32_t> nan_list;          // the pixels whose accumulated colour / moments are NaN or inf (kNanListCap entries)
+    DevicePtr<unsigned> nan_count;         // ... and its counters
+    DevicePtr<unsigned long long> sample_count;   // 64-bit counters 128 B apart: the sampled number of young pixels of a frame (TemporalArgs::sample_count)
+    HostPtr<unsigned long long> estimate_host;   // host-mapped: the latest sample a temporal launch has published (read without synchronising: some frames old)
+    int phase = 0;                         // which counter of each pair is the current one
+    bool pending = false;                  // a temporal launch wrote the masks / appended to the current counters and no moments launch has consumed them yet
+    bool complete() const { return masks && list && count && nan_list && nan_count && sample_count && estimate_host; }
+    void reset() { *this = YoungScratch(); }
+    unsigned long long* counter(bool next = false) const { return count.get() + (phase ^ (int)next) * svgf::kYoungCounterStride; }
+    unsigned* nan_counter(bool next = false) const { return nan_count.get() + (phase ^ (int)next); }
+    unsigned long long* sample_counter(bool next = false) const { return sample_count.get() + (phase ^ (int)next) * 16; }
+    void turn() { phase ^= 1; pending = false; }   // the moments launch has consumed the lists: the next frame appends to the counters this frame's temporal launch zeroed
+};
+
 }  // namespace svgf_host
 
 #ifndef SVGF_PREV_GUIDE_DEFAULT
@@ -48,7 +77,7 @@ template <class H, class F, class... A> hipError_t acquire(H& h, F make, A... ar
 struct svgf_ctx {
     int W = 0, H = 0;
     svgf_strip strip{};
-    int rb = 0, re = 0;                 // active compute rows (global)
+    int rb = 0, re = 0;                 // svgf_set_rows: the rows the stage entry points and svgf_denoise_frame compute (they pass them down; a strip driver's launches bring their own)
     svgf_params p{};
     int device = 0;
     hipStream_t stream = nullptr;
@@ -74,19 +103,9 @@ struct svgf_ctx {
     bool swap_pairs = false;               // frames_in_flight == 2: the next frame takes the other pair (false for the first one after the switch or a resize)
     bool in_flight = false;                // a frame's tail is on `side` and `stream` has not been made to wait for it yet
     unsigned long long in_flight_capture = 0;   // ... and the stream capture that tail was recorded in (0: none; svgf.h, Stream capture)
-    svgf_host::DevicePtr<unsigned long long> young_masks;   // scratch, temporal -> moments: per (row, 64-column segment) the lanes whose pixel (history < 4) needs the spatial estimate
-    svgf_host::DevicePtr<uint32_t> young_list;   // ... and the indices of the pixels of the partly young segments (svgf::young_list_entries)
-    svgf_host::DevicePtr<unsigned long long> young_count;   // ... two {appends, pixels} counters used in turn (the temporal launch of a frame zeroes the next frame's)
-    svgf_host::DevicePtr<unsigned> nan_count;    // two device counters of nan_list used in turn (the temporal launch of a frame zeroes the next frame's)
-    svgf_host::DevicePtr<unsigned long long> sample_count;   // two 64-bit device counters (128 B apart) used in turn: the sampled number of young pixels of a frame (TemporalArgs::sample_count)
-    svgf_host::HostPtr<unsigned long long> estimate_host;   // host-mapped: the latest sample a temporal launch has published (read without synchronising: some frames old)
+    svgf_host::YoungScratch young;         // temporal -> moments scratch (alloc_flags)
     bool adaptive_moments = true;          // svgf_set_adaptive_moments
-    bool dense_moments = false;            // the frame driver's current choice (hysteresis)
-    bool dense_now = false;                // the frame being enqueued is served by the streaming kernel (a cold or a crowded frame)
-    bool cold_now = false;                 // ... it is one of the first three after a reset
-    svgf_host::DevicePtr<uint32_t> nan_list;     // scratch, temporal -> moments: the pixels whose accumulated colour / moments are NaN or inf (kNanListCap entries)
-    int young_phase = 0;
-    bool young_pending = false;            // a temporal launch wrote the masks / appended to nan_count[young_phase] and no moments launch has consumed them yet
+    bool dense_moments = false;            // the drivers' current choice between the two moments kernels (hysteresis, choose_moments_kernel)
     int vy0 = 0, vy1 = 0;                  // global rows of the previous-frame planes that hold valid state (svgf_set_valid_rows; default: all held)
     svgf_host::DevicePtr<unsigned> halo_violations;   // strips: device counter of reprojections that left the rows this strip holds (temporal_kernel)
     int pingpong = 0;                      // PingPongInx, App.cu:374
@@ -149,18 +168,18 @@ hipError_t join_back(svgf_ctx* c, hipStream_t caller, unsigned long long capture
 int begin_frame(svgf_ctx* c);           // allocates what a frame needs and picks its pair of filter planes: c->filter
 void finish_frame(svgf_ctx* c, int result_index, const svgf_gbuffer* cur, bool guide_written);   // result, guide and ping-pong move on
 
-// the stages on caller- or driver-owned planes, rows [c->rb, c->re); the device is already current
-int temporal_moments_impl(svgf_ctx* c, const void* prev_colour, const void* radiance, void* colour_out, void* filter_out,
-                          const svgf_gbuffer* cur, const svgf_gbuffer* prev, const uint8_t* hist_prev, uint8_t* hist_cur,
-                          void* moments_cur, const void* moments_prev, int mrb, int mre, int feedback_follows, void* guide_out = nullptr,
-                          const void* guide_prev = nullptr, int dense = 0);
-void choose_moments_kernel(svgf_ctx* c, bool* cold, bool* crowded);   // frame / strip drivers, before the temporal launch of a frame (svgf_api.hip)
-int atrous_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide = nullptr);
-// one iteration over several row ranges in one launch, the first ranges signalled (the strip driver's edge rows; svgf_kernels.h: AtrousRanges)
+// the stages on caller- or driver-owned planes, each on the rows its caller passes (the context is not consulted for them); the device is already current
+// temporal launch on rows `rt`, moments launch on `rm` inside them; `choice`: which moments kernel (the stage entry point: the default)
+int temporal_moments_impl(svgf_ctx* c, Rows rt, Rows rm, MomentsChoice choice, const void* prev_colour, const void* radiance, void* colour_out,
+                          void* filter_out, const svgf_gbuffer* cur, const svgf_gbuffer* prev, const uint8_t* hist_prev, uint8_t* hist_cur,
+                          void* moments_cur, const void* moments_prev, int feedback_follows, void* guide_out = nullptr, const void* guide_prev = nullptr);
+MomentsChoice choose_moments_kernel(svgf_ctx* c, Rows rt);   // frame / strip drivers, before the temporal launch (rows rt) of a frame (svgf_api.hip)
+int atrous_impl(svgf_ctx* c, Rows rows, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide = nullptr);
+// one iteration over several row ranges in one launch, the first ranges signalled (the strip driver's edge rows; svgf_kernels.h: AtrousRanges); `hull` spans them
 bool atrous_ranges_ok(const svgf_ctx* c, int step);
-int atrous_ranges_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide, const svgf::AtrousRanges& r);
-// iterations 0 and 1 in one launch on rows [c->rb, c->re) (iteration 1's; iteration 0 and the feedback store cover 4 more rows either side)
-int atrous_pair_impl(svgf_ctx* c, const void* in, void* out, void* feedback, const svgf_gbuffer* g, const void* guide = nullptr);
+int atrous_ranges_impl(svgf_ctx* c, Rows hull, const void* in, void* out, void* feedback, const svgf_gbuffer* g, int step, int iteration, const void* guide, const svgf::AtrousRanges& r);
+// iterations 0 and 1 in one launch on `rows` (iteration 1's; iteration 0 and the feedback store cover 4 more rows either side)
+int atrous_pair_impl(svgf_ctx* c, Rows rows, const void* in, void* out, void* feedback, const svgf_gbuffer* g, const void* guide = nullptr);
 bool can_fuse01(const svgf_ctx* c);     // the drivers run iterations 0 and 1 as one launch
 const void* prev_guide_for(const svgf_ctx* c, const svgf_gbuffer* cur, const svgf_gbuffer* prev);   // the guide plane that stands in for `prev`, or null
 bool use_guide(const svgf_ctx* c);      // the frame / strip drivers repack {depth, ddepth, normal, instance ID} for the iterations (any storage, >= 1 iteration, LDS kernels)

@@ -195,14 +195,7 @@ bool make_geo(int W, int H, int rank, int world, int steps, int plan, int moment
     return world <= 1 || smallest >= g.halo_max;
 }
 
-struct Rows { int a, b; };
 Rows grown(const svgf_strip_plan_geo& g, int H, int ext) { return Rows{std::max(0, g.own0 - ext), std::min(H, g.own1 + ext)}; }
-
-
-}  // namespace
-
-
-namespace {
 
 size_t row_bytes(const svgf_strips* s, int plane) {
     const size_t px = (size_t)s->W;
@@ -474,15 +467,14 @@ Cut cut_rows(const svgf_strips* s, const svgf_strips::Local& l, const Step& st) 
 // svgf_kernels.h: AtrousRanges — what Wait::Signal waits for), `then` behind them; no `first`: a plain launch over `then`.  Timed over the rows it covers.
 int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, const Step& st, int src, const svgf_gbuffer* cur, std::initializer_list<Rows> first, Rows then) {
     svgf::AtrousRanges r{};
-    int rb = then.a, re = then.b, rows = 0;           // (rb, re: the hull of the ranges — the ranges launch reads only the ranges)
-    auto add = [&](Rows x) { rb = std::min(rb, x.a); re = std::max(re, x.b); if (x.b > x.a) { r.yb[r.n] = x.a; r.ye[r.n] = x.b; r.n++; rows += x.b - x.a; } };
+    Rows hull = then; int rows = 0;                   // (the hull of the ranges — the ranges launch reads only the ranges)
+    auto add = [&](Rows x) { hull = Rows{std::min(hull.a, x.a), std::max(hull.b, x.b)}; if (x.b > x.a) { r.yb[r.n] = x.a; r.ye[r.n] = x.b; r.n++; rows += x.b - x.a; } };
     for (Rows x : first) add(x);
     r.nfirst = r.n;
     add(then);
     if (!rows) return SVGF_OK;
     svgf_ctx* c = l.ctx;
     DeviceGuard dg(l.device);
-    c->rb = rb; c->re = re;
     const bool timed = s->timing_every > 0 && ((s->frame_no - s->timing_base) % s->timing_every) == 0 && l.rank == s->local[0].rank;
     Event e0, e1;
     if (timed) {
@@ -497,8 +489,8 @@ int launch_atrous_rows(svgf_strips* s, svgf_strips::Local& l, const Step& st, in
     if (first.size()) {
         const int k = signal_slot(l);
         r.signal = l.edge_signal[k].get(); r.arrivals = l.edge_arrivals.get() + 64 * k; r.value = ++l.edge_value[k];
-        rc = atrous_ranges_impl(c, in, out, feedback, cur, 1 << st.iter, st.iter, guide, r);
-    } else rc = st.pair ? atrous_pair_impl(c, in, out, feedback, cur, guide) : atrous_impl(c, in, out, feedback, cur, 1 << st.iter, st.iter, guide);
+        rc = atrous_ranges_impl(c, hull, in, out, feedback, cur, 1 << st.iter, st.iter, guide, r);
+    } else rc = st.pair ? atrous_pair_impl(c, hull, in, out, feedback, cur, guide) : atrous_impl(c, hull, in, out, feedback, cur, 1 << st.iter, st.iter, guide);
     if (rc != SVGF_OK) return sfail(s, rc, c->err);
     if (timed) {
         SVGF_SHIP(s, hipEventRecord(e1.get(), c->stream));
@@ -849,15 +841,13 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         const svgf_gbuffer* pv = prev ? &prev[k] : &cur[k];
         if (!pv->motion) pv = &cur[k];
         const Rows rt = grown(l.g, s->H, l.g.ext_temporal), rm = grown(l.g, s->H, l.g.ext_moments);
-        c->rb = rt.a; c->re = rt.b;
         void* guide = use_guide(c) ? c->guide.get() : nullptr;      // as svgf_denoise_frame: the temporal launch repacks {depth, ddepth, normal} for the iterations
         const void* guide_prev = prev_guide_for(c, &cur[k], pv);   // the previous frame's guide plane stands in for its G-buffer (all held rows)
         c->guide_prev_valid = false;                               // until this frame has written its own (finish_frame below)
         // which kernel serves the strip's young pixels (svgf_api.hip: every rank chooses for itself, the results do not depend on it)
-        bool cold = false, crowded = false;
-        choose_moments_kernel(c, &cold, &crowded);
-        int rc = temporal_moments_impl(c, c->colour[1 - P].get(), radiance[k], c->colour[P].get(), c->filter[0].get(), &cur[k], pv, c->hist[1 - P].get(),
-                                       c->hist[P].get(), c->moments[P].get(), c->moments[1 - P].get(), rm.a, rm.b, s->steps >= 1 && !crowded, guide, guide_prev, cold || crowded);
+        const MomentsChoice choice = choose_moments_kernel(c, rt);
+        int rc = temporal_moments_impl(c, rt, rm, choice, c->colour[1 - P].get(), radiance[k], c->colour[P].get(), c->filter[0].get(), &cur[k], pv, c->hist[1 - P].get(),
+                                       c->hist[P].get(), c->moments[P].get(), c->moments[1 - P].get(), s->steps >= 1 && !choice.crowded, guide, guide_prev);
         // (the temporal launch also writes the guide texels of the rows the strip holds beyond the temporal rows: the a-trous halos
         // of the later iteration groups and the next frame's reprojection read them)
         if (rc != SVGF_OK) return sfail(s, rc, c->err);
@@ -879,7 +869,6 @@ int svgf_strips_frame(svgf_strips* s, const void* const* radiance, const svgf_gb
         }
         if (aside) SVGF_SHIP(s, join_back(c, l.compute, 0));       // this frame's tail is the frame in flight now
         else if (int rc = join_side(c, l.compute); rc != SVGF_OK) return sfail(s, rc, c->err);   // this frame never left the filter stream: the one in flight is ordered behind it
-        c->rb = c->strip.own_begin; c->re = c->strip.own_end;
         if (results) results[k] = c->filter[pp[k]].get();
         finish_frame(c, pp[k], &cur[k], use_guide(c));
     }
