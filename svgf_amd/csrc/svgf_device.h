@@ -74,6 +74,15 @@ __device__ __forceinline__ float3 normal_of(uint2 n) {
     float2 a = unpack_h2(n.x), b = unpack_h2(n.y);
     return make_float3(a.x, a.y, b.x);
 }
+// A raw normal texel whose three components are all +-0: the G-buffer's cleared sky texels (n.n' = 0 against every tap)
+__device__ __forceinline__ bool is_zero_normal(uint2 n) { return ((n.x & 0x7fff7fffu) | (n.y & 0x7fffu)) == 0u; }
+// sparse_colour (frame driver): the temporal launch stored an old (history >= 4), non-sky texel's colour only into the moments stage's
+// `out` plane (same value); z_raw is the texel's depth as stored (depth 0 or literally 1e30f: sky)
+__device__ __forceinline__ bool colour_in_out(int sparse_colour, float z_raw, int hist) { return sparse_colour && z_raw != 0.0f && z_raw != kSkyZ && hist >= 4; }
+// The six sums of a moments estimate hold a NaN
+__device__ __forceinline__ bool sums_hold_nan(float sw, float sr, float sg, float sb, float sm1, float sm2) {
+    return __builtin_isunordered(sw, sm2) | __builtin_isunordered(sr, sg) | __builtin_isunordered(sb, sm1);
+}
 // One guide texel (16 B): what the wavelet iterations and the NEXT frame's reprojection test read of a G-buffer texel:
 // {depth, ddepth} as stored (raw: depth_of() is applied by the reader), (nx, ny) half bits, (nz, instance ID) half bits.
 __device__ __forceinline__ uint4 guide_texel(float4 motion, uint2 normal, uint2 uv) {
@@ -183,6 +192,9 @@ __device__ __forceinline__ void raw_load(RawPx<ST, DZ>& r, const PlaneRsrc& rs, 
 // "does any lane of the wave hold `pred`": HIP's __ballot() compares a materialised 0/1 (v_cndmask + v_cmp per call); the builtin folds
 // into the compare that produced the predicate.
 __device__ __forceinline__ bool wave_any(bool pred) { return __builtin_amdgcn_ballot_w64(pred) != 0ull; }
+
+// A lane's place among the set lanes of `mask` below it (a wave's append to a list: the offset from the base its first lane claimed)
+__device__ __forceinline__ unsigned lane_rank(unsigned long long mask, int lane) { return (unsigned)__builtin_popcountll(mask & ((1ull << lane) - 1ull)); }
 
 // Raw barrier: __syncthreads() would also wait for vmcnt(0), i.e. for the rows a step has just requested.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

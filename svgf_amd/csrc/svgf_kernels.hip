@@ -13,11 +13,6 @@
 #include "svgf_kernels.h"
 
 #include <algorithm>
-#include <numeric>
-#include <atomic>
-#include <vector>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 // The streaming a-trous kernels live in headers of their own (shared tap code: svgf_atrous_taps.h).
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(kBX* kBY) void temporal_kernel(Geo g, TemporalArgs 
     // A young pixel whose normal is exactly (0,0,0) — the G-buffer's cleared sky texels, which never pass the normal
     // test and stay young for ever — filters to exactly (0,0,0,0) when PhiNormal > 0 (see moments_pixel): written here too.
     const bool young = h < 4;
-    const bool zero_young = young && a.sky_zero && ((nc_raw.x & 0x7fff7fffu) | (nc_raw.y & 0x7fffu)) == 0u;
+    const bool zero_young = young && a.sky_zero && is_zero_normal(nc_raw);
     if (a.passthrough_out) {
         if (!young) Store<ST>::st4(a.passthrough_out, idx, oc);
         else if (zero_young) Store<ST>::st4(a.passthrough_out, idx, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(kBX* kBY) void temporal_kernel(Geo g, TemporalArgs 
                 else __hip_atomic_store(a.young_count + kYoungFlagOffset, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             base = __shfl(base, first);
-            if (listed && base != ~0u) a.young_list[base + (unsigned)__builtin_popcountll(ym & ((1ull << lane) - 1ull))] = (uint32_t)idx;
+            if (listed && base != ~0u) a.young_list[base + lane_rank(ym, lane)] = (uint32_t)idx;
         }
         // A pixel whose accumulated colour or moments are not finite (a NaN in the radiance, or in the history it reprojects onto:
         // the reference's clamps keep it, :63-83,398) is listed as well.  The shortcut above is only right while a zero-normal pixel's
@@ -181,8 +176,7 @@ __global__ __launch_bounds__(kBX* kBY) void temporal_kernel(Geo g, TemporalArgs 
             // queue 130 000 atomics on one word)
             if (lane == first) base = __hip_atomic_load(a.nan_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > kNanListCap
                                           ? kNanListCap : atomicAdd(a.nan_count, (unsigned)__builtin_popcountll(bad));
-            base = __shfl(base, first);
-            const unsigned at = base + (unsigned)__builtin_popcountll(bad & ((1ull << lane) - 1ull));
+            const unsigned at = __shfl(base, first) + lane_rank(bad, lane);
             if (((bad >> lane) & 1ull) && at < kNanListCap) a.nan_list[at] = (uint32_t)idx;
         }
     }
@@ -199,18 +193,12 @@ __device__ __forceinline__ void moments_pixel(const Geo& g, const MomentsArgs& a
     const float4 cc = Store<ST>::ld4(a.colour, idx);                  // :450 raw load
     if (!(h < 4.0f)) { Store<ST>::st4(a.out, idx, cc); return; }      // :521
 
-    const float lc = lum_exact(cc.x, cc.y, cc.z);
-    float zc, dzc;
-    depth_of(a.motion[idx], zc, dzc);
-    const uint2 nraw = a.normal[idx];
-    const float3 nc = normal_of(nraw);
+    const MomRefCentre c = mom_ref_centre(cc, a.motion[idx], a.normal[idx], a.phi_colour);
     // A centre whose normal is exactly (0,0,0) — the G-buffer's cleared sky texels — has n.n' = 0 for every tap, so with
     // phi_normal > 0 every weight is exp(..)*pow(0,phi_n) = 0 (edge_weight: exp2(-inf)): the sums are 0 x the taps, sumW clamps to
     // 1e-6 and the result is (0,0,0,0) (:505-516) — unless a tap is NaN or inf, whose product with 0 is NaN
     // (:498-499).  This kernel therefore takes no shortcut for such a centre; the frame driver's temporal launch does, and lists the
     // non-finite pixels so that the windows around them are redone (moments_young_kernel).
-    const float il = hw_rcp(a.phi_colour);                            // :460
-    const float phi_d = fmaxf(dzc, 1e-8f) * 3.0f;                     // :461
     float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sm1 = 0.f, sm2 = 0.f;
     const int R = a.radius;
     // One window row at a time, every load of the row issued before anything is consumed: two rounds of memory latency per
@@ -239,9 +227,7 @@ __device__ __forceinline__ void moments_pixel(const Geo& g, const MomentsArgs& a
         }
 #pragma unroll
         for (int k = 0; k <= 2 * RM; k++) {
-            // sparse_colour: the temporal launch stored an old, non-sky texel only into `out` (same value)
-            const bool in_out = a.sparse_colour && mq[k].z != 0.0f && mq[k].z != kSkyZ && hq[k] >= 4;
-            cp[k] = Store<ST>::ld4(in_out ? (const void*)a.out : a.colour, p[k]);   // :479 raw
+            cp[k] = Store<ST>::ld4(colour_in_out(a.sparse_colour, mq[k].z, hq[k]) ? (const void*)a.out : a.colour, p[k]);   // :479 raw
         }
 #pragma unroll
         for (int k = 0; k <= 2 * RM; k++) {
@@ -249,20 +235,13 @@ __device__ __forceinline__ void moments_pixel(const Geo& g, const MomentsArgs& a
             const int xx = k - RM;
             float zp, dzp;
             depth_of(mq[k], zp, dzp);                                 // :482
-            const float3 np = normal_of(nq[k]);
-            const float len = sqrtf((float)(xx * xx + yy * yy));      // :488
-            const float iz = (xx == 0 && yy == 0) ? 0.0f : hw_rcp(phi_d * len);   // phiDepth == 0 -> wZ = 0, :420
-            const float w = edge_weight(fabsf(lc - lum_exact(cp[k].x, cp[k].y, cp[k].z)), il, fabsf(zc - zp), iz, dot3_fma(nc, np), a.phi_normal);
+            const float w = mom_ref_weight(c, lum_exact(cp[k].x, cp[k].y, cp[k].z), zp, normal_of(nq[k]), xx, yy, a.phi_normal);
             sw += w;                                                  // :497-499
             sr = fmaf(cp[k].x, w, sr); sg = fmaf(cp[k].y, w, sg); sb = fmaf(cp[k].z, w, sb);
             sm1 = fmaf(mp[k].x, w, sm1); sm2 = fmaf(mp[k].y, w, sm2);
         }
     }
-    sw = fmaxf(sw, 1e-6f);                                            // :505
-    const float inv = 1.0f / sw;
-    sm1 *= inv; sm2 *= inv;
-    const float var = (sm2 - sm1 * sm1) * (4.0f / h);                 // :511-514
-    Store<ST>::st4(a.out, idx, make_float4(sr * inv, sg * inv, sb * inv, var));   // :516 unclamped
+    Store<ST>::st4(a.out, idx, moments_resolve(sw, sr, sg, sb, sm1, sm2, h));
 }
 
 // The same estimate for the pixels of the young list (disocclusions under a moving camera: a few tens of thousands of pixels along
@@ -275,12 +254,11 @@ __device__ __forceinline__ void moments_pixel(const Geo& g, const MomentsArgs& a
 // that holds them (__shfl = ds_bpermute: no memory), so the sums are accumulated in exactly the order — and to exactly the bits —
 // of moments_pixel.  The colour of a tap is fetched from BOTH planes it can live in (the choice depends on the tap's own depth /
 // history texel), which keeps every load of the window independent: one round of memory latency for the taps.
-// ARITH = 0: the tap weight as moments_pixel evaluates it (variant DIRECT, a radius other than 3, PhiNormal == 0: the stage calls then run
-// moments_pixel).  ARITH = 1: as moments_lds_kernel evaluates it (svgf_moments_lds.h, moments_taps49: the fused exponent on the same
-// bits) — the kernel the default variants run for a frame full of young pixels, so that which of the two serves a frame is a matter of
-// speed alone: the frame driver may switch between them from frame to frame without a bit of the results changing — next to NaN / inf
-// texels too: both evaluate a pixel whose fused-exponent sums hold a NaN again with the reference's `max(term, 0.0)` (:424) for all its taps,
-// and no other pixel.
+// ARITH = 0: the tap weight of moments_pixel, mom_ref_weight (variant DIRECT, a radius other than 3, PhiNormal == 0: the stage calls then run
+// moments_pixel).  ARITH = 1: that of moments_lds_kernel, mom_tap_exponent (svgf_moments_lds.h) — the kernel the default variants run for a
+// frame full of young pixels, so that which of the two serves a frame is a matter of speed alone: the frame driver may switch between them
+// from frame to frame without a bit of the results changing — next to NaN / inf texels too: both evaluate a pixel whose fused-exponent sums
+// hold a NaN again with the reference's `max(term, 0.0)` (:424) for all its taps, and no other pixel.
 template <int ST, int ARITH>
 __device__ __forceinline__ void moments_group8(const Geo& g, const MomentsArgs& a, bool valid, uint32_t pix) {
     constexpr int RM = 3, NW = 2 * RM + 1;
@@ -316,44 +294,29 @@ __device__ __forceinline__ void moments_group8(const Geo& g, const MomentsArgs& 
         ca[r] = Store<ST>::ld4(a.colour, p);                                           // :479 raw ...
         cb[r] = Store<ST>::ld4(a.sparse_colour ? (const void*)a.out : a.colour, p);    // ... or, for an old non-sky texel, where the temporal launch put it
     }
-    const float lc = lum_exact(cc.x, cc.y, cc.z);
-    float zc, dzc;
-    depth_of(mc, zc, dzc);
-    const float3 nc = normal_of(nraw);
-    const float il = hw_rcp(a.phi_colour);                            // :460
-    const float phi_d = fmaxf(dzc, 1e-8f) * 3.0f;                     // :461
-    // ARITH = 1: moments_lds_kernel's centre (svgf_moments_lds.h)
-    const float ncz1 = unpack_h2(nraw.y).x, il1 = il * kLog2e;
-    const float izb1 = hw_rcp(fmaxf(zc == kSkyZ ? 0.0f : mc.w, 1e-8f) * 3.0f) * kLog2e;
+    const MomRefCentre c = mom_ref_centre(cc, mc, nraw, a.phi_colour);
+    const MomCentre c1{c.lc, c.zc, unpack_h2(nraw.y).x, nraw.x, c.il * kLog2e};     // ARITH = 1
+    const float izb1 = mom_depth_scale(c.zc, mc.w);
     // this lane's seven taps: weight and the values the sums take from them
     float tw[NW], twx[NW], t0[NW], t1[NW], t2[NW];
     unsigned okbits = 0u;
 #pragma unroll
     for (int r = 0; r < NW; r++) {
         const int yy = r - RM;
-        const bool in_out = a.sparse_colour && tz[r] != 0.0f && tz[r] != kSkyZ && th[r] >= 4;
+        const bool in_out = colour_in_out(a.sparse_colour, tz[r], th[r]);
         const float4 va = ca[r], vb = cb[r];
         t0[r] = in_out ? vb.x : va.x; t1[r] = in_out ? vb.y : va.y; t2[r] = in_out ? vb.z : va.z;
         const float zp = tz[r] == 0.0f ? kSkyZ : tz[r];               // depth_of, :482
-        const float3 np = normal_of(tn[r]);
-        const float len = sqrtf((float)(xx * xx + yy * yy));          // :488 (IEEE sqrt of a small integer: the value a constant would have)
-        const float iz = (xx == 0 && yy == 0) ? 0.0f : hw_rcp(phi_d * len);   // phiDepth == 0 -> wZ = 0, :420
+        const float lum = lum_exact(t0[r], t1[r], t2[r]);
         if constexpr (ARITH == 0) {
-            tw[r] = edge_weight(fabsf(lc - lum_exact(t0[r], t1[r], t2[r])), il, fabsf(zc - zp), iz, dot3_fma(nc, np), a.phi_normal);
+            tw[r] = mom_ref_weight(c, lum, zp, normal_of(tn[r]), xx, yy, a.phi_normal);
         } else {
-            const int l2 = xx * xx + yy * yy;                         // moments_taps49's depth scale by tap distance (len_class7)
-            const float km = l2 == 1 ? 1.0f : l2 == 2 ? 0.70710678118654752f : l2 == 4 ? 0.5f : l2 == 5 ? 0.44721359549995794f : l2 == 8 ? 0.35355339059327376f
-                           : l2 == 9 ? 0.33333333333333333f : l2 == 10 ? 0.31622776601683794f : l2 == 13 ? 0.27735009811261456f : 0.23570226039551584f;
-            // both of moments_taps49's forms: the fused exponent (kTapsGeneral), and the reference's `max(term, 0.0)` = fmax, which drops a NaN
-            // term (:424, kTapsNaN) — the sums take the first; a pixel whose sums come out NaN takes the second for ALL its taps, below
-            const float d = clamp01(fmaf(unpack_h2(tn[r].y).x, ncz1, dot2_h2(tn[r].x, nraw.x)));
-            const float en = hw_log2(d) * a.phi_normal;
-            const float adl = fabsf(lum_exact(t0[r], t1[r], t2[r]) - lc);
-            const float dz = fabsf(zp - zc), izk = l2 == 1 ? izb1 : izb1 * km;
-            float e = fmaf(-adl, il1, en), ex = en - fmaxf(adl * il1, 0.0f);
-            if (l2 != 0) { e = fmaf(-dz, izk, e); ex -= fmaxf(dz * izk, 0.0f); }
-            tw[r] = hw_exp2(e);
-            twx[r] = hw_exp2(ex);
+            // both forms: the fused exponent (kTapsGeneral), and the reference's `max(term, 0.0)` = fmax, which drops a NaN term (:424,
+            // kTapsNaN) — the sums take the first; a pixel whose sums come out NaN takes the second for ALL its taps, below
+            const int l2 = xx * xx + yy * yy;
+            const float izk = l2 == 1 ? izb1 : izb1 * inv_len7(xx, yy), nz = unpack_h2(tn[r].y).x;
+            tw[r] = hw_exp2(mom_tap_exponent<kTapsGeneral>(c1, lum, zp, tn[r].x, nz, l2 == 0, izk, a.phi_normal, 0.0f));
+            twx[r] = hw_exp2(mom_tap_exponent<kTapsNaN>(c1, lum, zp, tn[r].x, nz, l2 == 0, izk, a.phi_normal, 0.0f));
         }
         okbits |= ok[r] ? 1u << r : 0u;
     }
@@ -384,9 +347,9 @@ __device__ __forceinline__ void moments_group8(const Geo& g, const MomentsArgs& 
     if constexpr (ARITH == 1) {
         // moments_lds_kernel's rule (svgf_moments_lds.h): a pixel whose sums hold a NaN — one with a NaN, inf - inf or 0 x inf in its window, and
         // no other — is evaluated again the reference's way; every other pixel keeps the fused exponent's bits, whichever kernel serves it
-        if (wave_any(__builtin_isunordered(sw, sm2) | __builtin_isunordered(sr, sg) | __builtin_isunordered(sb, sm1))) {
+        const bool redo = sums_hold_nan(sw, sr, sg, sb, sm1, sm2);
+        if (wave_any(redo)) {
             const float w1 = sw, r1 = sr, g1 = sg, b1 = sb, a1 = sm1, a2 = sm2;
-            const bool redo = __builtin_isunordered(w1, a2) | __builtin_isunordered(r1, g1) | __builtin_isunordered(b1, a1);
             sums(twx);
             if (!redo) { sw = w1; sr = r1; sg = g1; sb = b1; sm1 = a1; sm2 = a2; }
         }
@@ -395,11 +358,7 @@ __device__ __forceinline__ void moments_group8(const Geo& g, const MomentsArgs& 
     if (a.cold_only && !(h < 4.0f)) return;                           // already written by temporal_kernel (passthrough_out)
     if (!(h < 4.0f)) { Store<ST>::st4(a.out, idx, cc); return; }      // :521
     // (a zero-normal centre needs no special case: all its weights came out as exactly 0 above, see moments_pixel)
-    sw = fmaxf(sw, 1e-6f);                                            // :505
-    const float inv = 1.0f / sw;
-    sm1 *= inv; sm2 *= inv;
-    const float var = (sm2 - sm1 * sm1) * (4.0f / h);                 // :511-514
-    Store<ST>::st4(a.out, idx, make_float4(sr * inv, sg * inv, sb * inv, var));   // :516 unclamped
+    Store<ST>::st4(a.out, idx, moments_resolve(sw, sr, sg, sb, sm1, sm2, h));
 }
 
 template <int ST>
@@ -413,7 +372,8 @@ __global__ __launch_bounds__(kBX* kBY) void moments_kernel(Geo g, MomentsArgs a)
 // The 3x3 variant of the estimate (moments_radius = 1) with the neighbourhood shared through wave64 shuffles: a wave is
 // 64 consecutive pixels of a row; every lane loads its own column of rows y-1, y, y+1 once (coalesced) and takes the
 // columns x-1 / x+1 from its neighbour lanes (__shfl_up / __shfl_down); only lanes 0 and 63 fetch the column beyond the
-// wave.  3 row loads per plane instead of 9 gathers.  Same expressions in the same order as moments_pixel: bit-identical.
+// wave.  3 row loads per plane instead of 9 gathers.  The estimate is moments_pixel's (mom_ref_centre / mom_ref_weight /
+// moments_resolve on the same taps in the same order): bit-identical.
 struct MomTap { float cx, cy, cz, m1, m2, z; uint32_t n01, n2; };
 __device__ __forceinline__ MomTap shfl_tap(const MomTap& t, int dir) {
     MomTap r;
@@ -463,12 +423,7 @@ __global__ __launch_bounds__(kBX* kBY) void moments3x3_shfl_kernel(Geo g, Moment
     if (a.cold_only && !(h < 4.0f)) return;
     if (!(h < 4.0f)) { Store<ST>::st4(a.out, idx, Store<ST>::ld4(a.colour, idx)); return; }   // :521
     const MomTap& cc = own[1];
-    const float lc = lum_exact(cc.cx, cc.cy, cc.cz);
-    float zc, dzc;
-    depth_of(a.motion[idx], zc, dzc);
-    const float3 nc = normal_of(make_uint2(cc.n01, cc.n2));
-    const float il = hw_rcp(a.phi_colour);                            // :460
-    const float phi_d = fmaxf(dzc, 1e-8f) * 3.0f;                     // :461
+    const MomRefCentre c = mom_ref_centre(make_float4(cc.cx, cc.cy, cc.cz, 0.f), a.motion[idx], make_uint2(cc.n01, cc.n2), a.phi_colour);
     float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sm1 = 0.f, sm2 = 0.f;
 #pragma unroll
     for (int yy = -1; yy <= 1; yy++) {
@@ -478,20 +433,13 @@ __global__ __launch_bounds__(kBX* kBY) void moments3x3_shfl_kernel(Geo g, Moment
             const int px = x + xx;
             if (px < 0 || px >= g.W) continue;
             const MomTap& t = xx < 0 ? lft[yy + 1] : (xx == 0 ? own[yy + 1] : rgt[yy + 1]);
-            const float3 np = normal_of(make_uint2(t.n01, t.n2));
-            const float len = sqrtf((float)(xx * xx + yy * yy));      // :488
-            const float iz = (xx == 0 && yy == 0) ? 0.0f : hw_rcp(phi_d * len);
-            const float w = edge_weight(fabsf(lc - lum_exact(t.cx, t.cy, t.cz)), il, fabsf(zc - t.z), iz, dot3_fma(nc, np), a.phi_normal);
+            const float w = mom_ref_weight(c, lum_exact(t.cx, t.cy, t.cz), t.z, normal_of(make_uint2(t.n01, t.n2)), xx, yy, a.phi_normal);
             sw += w;                                                  // :497-499
             sr = fmaf(t.cx, w, sr); sg = fmaf(t.cy, w, sg); sb = fmaf(t.cz, w, sb);
             sm1 = fmaf(t.m1, w, sm1); sm2 = fmaf(t.m2, w, sm2);
         }
     }
-    sw = fmaxf(sw, 1e-6f);                                            // :505
-    const float inv = 1.0f / sw;
-    sm1 *= inv; sm2 *= inv;
-    const float var = (sm2 - sm1 * sm1) * (4.0f / h);                 // :511-514
-    Store<ST>::st4(a.out, idx, make_float4(sr * inv, sg * inv, sb * inv, var));   // :516 unclamped
+    Store<ST>::st4(a.out, idx, moments_resolve(sw, sr, sg, sb, sm1, sm2, h));
 }
 
 // Steady state inside the frame driver: the temporal launch already copied every pixel with history >= 4 and told this launch where
@@ -616,7 +564,7 @@ __global__ __launch_bounds__(256, 3) void moments_young_kernel(Geo g, MomentsArg
     const unsigned wave = blockIdx.x * 4u + (unsigned)w, nwaves = gridDim.x * 4u;
     auto shortcut_px = [&](bool valid, uint32_t q) {             // young, with an all-zero normal
         const uint2 nq = a.normal[q];
-        return valid && a.hist[q] < 4 && ((nq.x & 0x7fff7fffu) | (nq.y & 0x7fffu)) == 0u;
+        return valid && a.hist[q] < 4 && is_zero_normal(nq);
     };
     if (nn <= kNanListCap) {
         for (unsigned i = wave; i < nn; i += nwaves) {
@@ -749,6 +697,30 @@ __device__ __forceinline__ float3 taa_clamp(float3 ya, const float3 (&y)[9]) {
 }
 __device__ __forceinline__ bool any_nan3(float3 v) { return __builtin_isunordered(v.x, v.y) | (v.z != v.z); }
 
+// :310-317,320-328: the neighbourhood as indices into the three sample columns / rows: the centre, the plus-shaped and the diagonal neighbours
+constexpr int kTaaNx[9] = {1, 2, 0, 1, 1, 2, 0, 2, 0}, kTaaNy[9] = {1, 1, 1, 2, 0, 2, 2, 0, 0};
+
+// Everything after the neighbourhood is gathered (:302-355), for both TAA kernels, in two steps — which clamp a wave takes is the kernel's rule,
+// and it looks at the blended colour.  taa_blend: last, c0 are the previous output and the filtered frame at the sample (clamped loads) -> the
+// gamma-2 blend in YUV.  taa_resolve: y is the neighbourhood in YUV (kTaaNx / kTaaNy order), exact the choice of taa_clamp's form.
+__device__ __forceinline__ float3 taa_blend(float4 last, float4 c0) {
+    const float mix = fminf(last.w, 0.5f);                                // :302 (CUDA's min(float, double) is fmin: a NaN alpha gives 0.5)
+    const float3 aa = make_float3(sqrtf(mix_exact(last.x * last.x, c0.x * c0.x, mix)), sqrtf(mix_exact(last.y * last.y, c0.y * c0.y, mix)),
+                                  sqrtf(mix_exact(last.z * last.z, c0.z * c0.z, mix)));   // :307-308
+    return enc_yuv(aa);                                                   // :319
+}
+template <int ST>
+__device__ __forceinline__ void taa_resolve(float3 ya, const float3 (&y)[9], bool exact, void* out, size_t at) {
+    ya = exact ? taa_clamp<true>(ya, y) : taa_clamp<false>(ya, y);
+    // :277-285; pow(x, 0.5) = sqrt(x), NaN for negative x
+    float r = sqrtf((ya.x * 1.0f + ya.y * 0.0f) + ya.z * 1.13983f);
+    float g = sqrtf((ya.x * 1.0f + ya.y * -0.39465f) + ya.z * -0.58060f);
+    float b = sqrtf((ya.x * 1.0f + ya.y * 2.03211f) + ya.z * 0.0f);
+    if (r != r || g != g || b != b) { r = 0.f; g = 0.f; b = 0.f; }        // :351
+    const float4 o = make_float4(to_srgb(r), to_srgb(g), to_srgb(b), 1.0f);   // :353
+    Store<ST>::st4(out, at, clamp01_ref(o));                              // :355 imageStore
+}
+
 template <int ST>
 __global__ __launch_bounds__(kBX* kBY) void taa_kernel(Geo g, const void* filtered, const void* history, void* out) {
     keep_nan_in_clamps();                                                 // imageLoad keeps a NaN (svgf_device.h)
@@ -761,35 +733,23 @@ __global__ __launch_bounds__(kBX* kBY) void taa_kernel(Geo g, const void* filter
     const int sy[3] = {tex_coord(v - ih, g.H), tex_coord(v, g.H), tex_coord(v + ih, g.H)};
     auto at = [&](const void* img, int ix, int iy) { return clamp01_ref(Store<ST>::ld4(img, (size_t)(sy[iy] - g.y0) * g.W + sx[ix])); };
     const float4 last = at(history, 1, 1);                                // :299
-    const float mix = fminf(last.w, 0.5f);                                // :302 (CUDA's min(float, double) is fmin: a NaN alpha gives 0.5)
     const float4 c0 = at(filtered, 1, 1);                                 // :305
-    float3 aa = make_float3(sqrtf(mix_exact(last.x * last.x, c0.x * c0.x, mix)), sqrtf(mix_exact(last.y * last.y, c0.y * c0.y, mix)),
-                            sqrtf(mix_exact(last.z * last.z, c0.z * c0.z, mix)));   // :307-308
-    float3 ya = enc_yuv(aa);                                              // :319
-    // :310-317,320-328: the centre, the plus-shaped and the diagonal neighbours
+    const float3 ya = taa_blend(last, c0);
     float3 nbv[9];
-    const int nx[9] = {1, 2, 0, 1, 1, 2, 0, 2, 0}, ny[9] = {1, 1, 1, 2, 0, 2, 2, 0, 0};
     bool nan_in = any_nan3(ya);
 #pragma unroll
     for (int k = 0; k < 9; k++) {
-        const float4 c = k == 0 ? c0 : at(filtered, nx[k], ny[k]);
+        const float4 c = k == 0 ? c0 : at(filtered, kTaaNx[k], kTaaNy[k]);
         nbv[k] = enc_yuv(make_float3(c.x, c.y, c.z));
         nan_in = nan_in | any_nan3(nbv[k]);
     }
-    ya = wave_any(nan_in) ? taa_clamp<true>(ya, nbv) : taa_clamp<false>(ya, nbv);
-    // :277-285; pow(x, 0.5) = sqrt(x), NaN for negative x
-    float r = sqrtf((ya.x * 1.0f + ya.y * 0.0f) + ya.z * 1.13983f);
-    float gg = sqrtf((ya.x * 1.0f + ya.y * -0.39465f) + ya.z * -0.58060f);
-    float b = sqrtf((ya.x * 1.0f + ya.y * 2.03211f) + ya.z * 0.0f);
-    if (r != r || gg != gg || b != b) { r = 0.f; gg = 0.f; b = 0.f; }     // :351
-    const float4 o = make_float4(to_srgb(r), to_srgb(gg), to_srgb(b), 1.0f);   // :353
-    Store<ST>::st4(out, (size_t)(y - g.y0) * g.W + x, clamp01_ref(o));   // :355 imageStore
+    taa_resolve<ST>(ya, nbv, wave_any(nan_in), out, (size_t)(y - g.y0) * g.W + x);
 }
 
 // The same stage with the neighbourhood's YUV values computed ONCE per texel: a workgroup covers 64 x 8 pixels, encodes
 // the 68 x 12 filtered texels its samples can touch into LDS (the nearest-texel coordinates floor(uv*(N-1)) land one to
 // three texels up-left of the pixel, depending on fp32 rounding), and every pixel takes its nine neighbours from there
-// instead of nine gathers + nine YUV encodings.  Same functions on the same inputs: bit-identical to taa_kernel.
+// instead of nine gathers + nine YUV encodings.  The same enc_yuv on the same texels, then the same taa_resolve: bit-identical to taa_kernel.
 constexpr int kTaaW = 68, kTaaH = 12, kTaaRows = 8;
 template <int ST>
 __global__ __launch_bounds__(kBX* kBY) void taa_lds_kernel(Geo g, const void* filtered, const void* history, void* out) {
@@ -832,23 +792,13 @@ __global__ __launch_bounds__(kBX* kBY) void taa_lds_kernel(Geo g, const void* fi
         auto nb = [&](int ix, int iy) { const float4 e = yuv[sy[iy] - (yb - 3)][sx[ix] - (x0 - 3)]; return make_float3(e.x, e.y, e.z); };
         const size_t ci = (size_t)(sy[1] - g.y0) * g.W + sx[1];
         const float4 last = clamp01_ref(Store<ST>::ld4(history, ci));     // :299
-        const float mix = fminf(last.w, 0.5f);                            // :302 (CUDA's min(float, double) is fmin)
         const float4 c0 = clamp01_ref(Store<ST>::ld4(filtered, ci));      // :305
-        float3 aa = make_float3(sqrtf(mix_exact(last.x * last.x, c0.x * c0.x, mix)), sqrtf(mix_exact(last.y * last.y, c0.y * c0.y, mix)),
-                                sqrtf(mix_exact(last.z * last.z, c0.z * c0.z, mix)));   // :307-308
-        float3 ya = enc_yuv(aa);                                          // :319
-        const int nx[9] = {1, 2, 0, 1, 1, 2, 0, 2, 0}, ny[9] = {1, 1, 1, 2, 0, 2, 2, 0, 0};
+        const float3 ya = taa_blend(last, c0);
         float3 nbv[9];
 #pragma unroll
-        for (int k = 0; k < 9; k++) nbv[k] = nb(nx[k], ny[k]);
+        for (int k = 0; k < 9; k++) nbv[k] = nb(kTaaNx[k], kTaaNy[k]);
         // (taa_kernel takes the exact form per wave; a tile that holds a NaN takes it for all its waves: for NaN-free values the two forms agree)
-        ya = (tile_exact || wave_any(any_nan3(ya))) ? taa_clamp<true>(ya, nbv) : taa_clamp<false>(ya, nbv);
-        float rr = sqrtf((ya.x * 1.0f + ya.y * 0.0f) + ya.z * 1.13983f);
-        float gg = sqrtf((ya.x * 1.0f + ya.y * -0.39465f) + ya.z * -0.58060f);
-        float bb = sqrtf((ya.x * 1.0f + ya.y * 2.03211f) + ya.z * 0.0f);
-        if (rr != rr || gg != gg || bb != bb) { rr = 0.f; gg = 0.f; bb = 0.f; }     // :351
-        const float4 o = make_float4(to_srgb(rr), to_srgb(gg), to_srgb(bb), 1.0f);  // :353
-        Store<ST>::st4(out, (size_t)(y - g.y0) * g.W + x, clamp01_ref(o));    // :355 imageStore
+        taa_resolve<ST>(ya, nbv, tile_exact || wave_any(any_nan3(ya)), out, (size_t)(y - g.y0) * g.W + x);
     }
 }
 
@@ -898,16 +848,23 @@ __global__ __launch_bounds__(kBX* kBY) void pack_gbuffer_kernel(Geo g, PackArgs 
 }
 
 
-inline dim3 grid_for(const Geo& g) { return dim3((g.W + kBX - 1) / kBX, (g.ye - g.yb + kBY - 1) / kBY); }
+// a wave is 64 consecutive pixels of a row, a workgroup kBY waves; its pixels are `block_rows` of the launch rows
+constexpr dim3 kBlock(kBX, kBY);
+inline dim3 grid_for(const Geo& g, int block_rows = kBY) { return dim3((g.W + kBX - 1) / kBX, (g.ye - g.yb + block_rows - 1) / block_rows); }
+
+// A launch's run-time 0 / 1 choices (the storage type, a kernel's mode) as template arguments: f receives one std::integral_constant per flag.
+template <typename F> auto pick(bool a, F f) { return a ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{}); }
+template <typename F> auto pick(bool a, bool b, F f) { return pick(a, [&](auto A) { return pick(b, [&](auto B) { return f(A, B); }); }); }
 
 }  // namespace
 
 hipError_t launch_temporal(const Geo& g, int storage, const TemporalArgs& a, hipStream_t s) {
     if (g.ye <= g.yb) return hipSuccess;
     const int ylo = a.guide_out ? std::min(g.yb, a.guide_lo) : g.yb, yhi = a.guide_out ? std::max(g.ye, a.guide_hi) : g.ye;
-    const dim3 block(kBX, kBY), grid((g.W + kBX - 1) / kBX, (yhi - ylo + kBY - 1) / kBY);
-    if (storage == 0) temporal_kernel<0><<<grid, block, 0, s>>>(g, a);
-    else temporal_kernel<1><<<grid, block, 0, s>>>(g, a);
+    Geo covered = g;                                // the compute rows and the guide rows around them
+    covered.yb = ylo; covered.ye = yhi;
+    const dim3 grid = grid_for(covered);
+    pick(storage != 0, [&](auto ST) { temporal_kernel<ST.value><<<grid, kBlock, 0, s>>>(g, a); });
     return hipGetLastError();
 }
 
@@ -916,12 +873,10 @@ hipError_t launch_moments(const Geo& g, int storage, const MomentsArgs& a, bool 
     // dense: the caller knows (nearly) every pixel is young — the LDS-streaming kernel; it needs the reference's
     // radius and a non-degenerate PhiNormal (the fused exponent would see 0 * -inf)
     if (a.dense && a.radius == kMR && a.phi_normal != 0.0f)
-        return storage == 0 ? launch_moments_lds<0>(g, a, s) : launch_moments_lds<1>(g, a, s);
+        return pick(storage != 0, [&](auto ST) { return launch_moments_lds<ST.value>(g, a, s); });
     // the 3x3 variant on a plane full of young pixels (stage call, or the first frames of a sequence): wave64 shuffles
     if (a.radius == 1 && !direct && (a.dense || !a.cold_only)) {
-        const dim3 block(kBX, kBY), grid = grid_for(g);
-        if (storage == 0) moments3x3_shfl_kernel<0><<<grid, block, 0, s>>>(g, a);
-        else moments3x3_shfl_kernel<1><<<grid, block, 0, s>>>(g, a);
+        pick(storage != 0, [&](auto ST) { moments3x3_shfl_kernel<ST.value><<<grid_for(g), kBlock, 0, s>>>(g, a); });
         return hipGetLastError();
     }
     if (a.cold_only && a.young_masks) {
@@ -932,44 +887,38 @@ hipError_t launch_moments(const Geo& g, int storage, const MomentsArgs& a, bool 
         scan *= kScanSplit;
         // the arithmetic of the kernel the stage calls / the dense frames of this configuration run (moments_group8)
         const bool lds_arith = !direct && a.radius == kMR && a.phi_normal != 0.0f;
-        if (storage == 0) { if (lds_arith) moments_young_kernel<0, 1><<<scan + walk, 256, 0, s>>>(g, a, scan); else moments_young_kernel<0, 0><<<scan + walk, 256, 0, s>>>(g, a, scan); }
-        else { if (lds_arith) moments_young_kernel<1, 1><<<scan + walk, 256, 0, s>>>(g, a, scan); else moments_young_kernel<1, 0><<<scan + walk, 256, 0, s>>>(g, a, scan); }
+        pick(storage != 0, lds_arith, [&](auto ST, auto ARITH) { moments_young_kernel<ST.value, ARITH.value><<<scan + walk, 256, 0, s>>>(g, a, scan); });
         return hipGetLastError();
     }
-    const dim3 block(kBX, kBY), grid = grid_for(g);
-    if (storage == 0) moments_kernel<0><<<grid, block, 0, s>>>(g, a);
-    else moments_kernel<1><<<grid, block, 0, s>>>(g, a);
+    pick(storage != 0, [&](auto ST) { moments_kernel<ST.value><<<grid_for(g), kBlock, 0, s>>>(g, a); });
     return hipGetLastError();
+}
+
+// The LDS-streaming kernels serve this step: a power of two up to 64, any variant but DIRECT, and PhiNormal != 0 — phi_normal == 0
+// (pow(x,0) = 1 even at x = 0) is left to the direct kernel: the fused exponent would see 0 * -inf
+static bool lds_serves(int variant, const AtrousArgs& a) {
+    const bool step_ok = a.step == 1 || a.step == 2 || a.step == 4 || a.step == 8 || a.step == 16 || a.step == 32 || a.step == 64;
+    return variant != 1 /* SVGF_VARIANT_DIRECT */ && step_ok && a.phi_normal != 0.0f;
 }
 
 hipError_t launch_atrous(const Geo& g, int storage, int variant, const AtrousArgs& a, hipStream_t s) {
     if (g.ye <= g.yb) return hipSuccess;
-    const bool lds_ok = a.step == 1 || a.step == 2 || a.step == 4 || a.step == 8 || a.step == 16 || a.step == 32 || a.step == 64;
-    // phi_normal == 0 (pow(x,0) = 1 even at x = 0) is left to the direct kernel: the fused exponent would see 0 * -inf
-    if (variant != 1 /* SVGF_VARIANT_DIRECT */ && lds_ok && a.phi_normal != 0.0f)
-        return storage == 0 ? launch_atrous_lds_step<0>(g, a, s) : launch_atrous_lds_step<1>(g, a, s);
-    const dim3 block(kBX, kBY), grid = grid_for(g);
-    if (storage == 0) atrous_direct_kernel<0><<<grid, block, 0, s>>>(g, a);
-    else atrous_direct_kernel<1><<<grid, block, 0, s>>>(g, a);
+    if (lds_serves(variant, a)) return pick(storage != 0, [&](auto ST) { return launch_atrous_lds_step<ST.value>(g, a, s); });
+    pick(storage != 0, [&](auto ST) { atrous_direct_kernel<ST.value><<<grid_for(g), kBlock, 0, s>>>(g, a); });
     return hipGetLastError();
 }
 
 // The strip driver's one-launch iteration (AtrousRanges, svgf_kernels.h): LDS-streaming kernel only.
-bool atrous_ranges_available(int variant, const AtrousArgs& a) {
-    const bool lds_ok = a.step == 1 || a.step == 2 || a.step == 4 || a.step == 8 || a.step == 16 || a.step == 32 || a.step == 64;
-    return variant != 1 /* SVGF_VARIANT_DIRECT */ && lds_ok && a.phi_normal != 0.0f;
-}
+bool atrous_ranges_available(int variant, const AtrousArgs& a) { return lds_serves(variant, a); }
 hipError_t launch_atrous_ranges(const Geo& g, int storage, const AtrousArgs& a, const AtrousRanges& r, hipStream_t s) {
-    return storage == 0 ? launch_atrous_lds_step<0>(g, a, s, &r) : launch_atrous_lds_step<1>(g, a, s, &r);
+    return pick(storage != 0, [&](auto ST) { return launch_atrous_lds_step<ST.value>(g, a, s, &r); });
 }
 
-// Iterations 0 and 1 (steps 1 and 2) in one launch (svgf_atrous_fused.h); Geo's launch rows are iteration 1's.
-bool atrous_fused_available(int variant, const AtrousArgs& a) {
-    return variant != 1 /* SVGF_VARIANT_DIRECT */ && a.phi_normal != 0.0f;
-}
+// Iterations 0 and 1 (steps 1 and 2) in one launch (svgf_atrous_fused.h); Geo's launch rows are iteration 1's, a.step iteration 0's.
+bool atrous_fused_available(int variant, const AtrousArgs& a) { return lds_serves(variant, a); }
 hipError_t launch_atrous_fused(const Geo& g, int storage, const AtrousArgs& a, hipStream_t s) {
     if (g.ye <= g.yb) return hipSuccess;
-    return storage == 0 ? launch_atrous_fused12<0>(g, a, s) : launch_atrous_fused12<1>(g, a, s);
+    return pick(storage != 0, [&](auto ST) { return launch_atrous_fused12<ST.value>(g, a, s); });
 }
 
 // Albedo demodulation (MODE 0) / re-modulation (MODE 1), SURVEY.md 8f-4: pointwise, IEEE division (bit-exact vs the oracle).
@@ -995,31 +944,23 @@ __global__ __launch_bounds__(kBX* kBY) void albedo_kernel(Geo g, const void* in,
 
 hipError_t launch_albedo(const Geo& g, int storage, int mode, const void* in, const void* albedo, void* out, hipStream_t s) {
     if (g.ye <= g.yb) return hipSuccess;
-    const dim3 block(kBX, kBY), grid = grid_for(g);
-    if (storage == 0) { if (mode == 0) albedo_kernel<0, 0><<<grid, block, 0, s>>>(g, in, albedo, out); else albedo_kernel<0, 1><<<grid, block, 0, s>>>(g, in, albedo, out); }
-    else { if (mode == 0) albedo_kernel<1, 0><<<grid, block, 0, s>>>(g, in, albedo, out); else albedo_kernel<1, 1><<<grid, block, 0, s>>>(g, in, albedo, out); }
+    pick(storage != 0, mode != 0, [&](auto ST, auto MODE) { albedo_kernel<ST.value, MODE.value><<<grid_for(g), kBlock, 0, s>>>(g, in, albedo, out); });
     return hipGetLastError();
 }
 
 hipError_t launch_pack_gbuffer(const Geo& g, const PackArgs& a, hipStream_t s) {
     if (g.ye <= g.yb) return hipSuccess;
-    pack_gbuffer_kernel<<<grid_for(g), dim3(kBX, kBY), 0, s>>>(g, a);
+    pack_gbuffer_kernel<<<grid_for(g), kBlock, 0, s>>>(g, a);
     return hipGetLastError();
 }
 
 
 hipError_t launch_taa(const Geo& g, int storage, const void* filtered, const void* history, void* out, bool direct, hipStream_t s) {
     if (g.ye <= g.yb) return hipSuccess;
-    const dim3 block(kBX, kBY);
-    if (direct) {
-        const dim3 grid = grid_for(g);
-        if (storage == 0) taa_kernel<0><<<grid, block, 0, s>>>(g, filtered, history, out);
-        else taa_kernel<1><<<grid, block, 0, s>>>(g, filtered, history, out);
-    } else {
-        const dim3 grid((g.W + kBX - 1) / kBX, (g.ye - g.yb + kTaaRows - 1) / kTaaRows);
-        if (storage == 0) taa_lds_kernel<0><<<grid, block, 0, s>>>(g, filtered, history, out);
-        else taa_lds_kernel<1><<<grid, block, 0, s>>>(g, filtered, history, out);
-    }
+    pick(storage != 0, [&](auto ST) {
+        if (direct) taa_kernel<ST.value><<<grid_for(g), kBlock, 0, s>>>(g, filtered, history, out);
+        else taa_lds_kernel<ST.value><<<grid_for(g, kTaaRows), kBlock, 0, s>>>(g, filtered, history, out);
+    });
     return hipGetLastError();
 }
 

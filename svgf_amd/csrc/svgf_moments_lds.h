@@ -35,18 +35,80 @@ constexpr int kMTapDepth = 3;                // LDS reads run this many taps ahe
 constexpr int kMRounds = 4;                  // workgroups per resident slot of the chip the bands are cut for
 constexpr int kMRecBytes = 36;
 
-__device__ __forceinline__ constexpr int len_class7(int xx, int yy) {   // |(xx,yy)|^2 in {1,2,4,5,8,9,10,13,18}
-    const int l2 = xx * xx + yy * yy;
-    return l2 == 1 ? 0 : l2 == 2 ? 1 : l2 == 4 ? 2 : l2 == 5 ? 3 : l2 == 8 ? 4 : l2 == 9 ? 5 : l2 == 10 ? 6 : l2 == 13 ? 7 : 8;
+// The nine distances of a 7x7 window's taps from its centre, as classes 0 .. 8: |(xx,yy)|^2 ...
+constexpr int kLen2_7[9] = {1, 2, 4, 5, 8, 9, 10, 13, 18};
+__device__ __forceinline__ constexpr int len_class7(int xx, int yy) {
+    int k = 8;
+    for (int i = 7; i >= 0; i--) k = xx * xx + yy * yy == kLen2_7[i] ? i : k;
+    return k;
 }
 
-struct MomCentre { float lc, zc, ncz; uint32_t nc01; float il; float iz[9]; };
+// ... and 1 / |(xx,yy)|: the depth term's scale by tap distance (:488)
+constexpr float kInvLen7[9] = {1.0f, 0.70710678118654752f, 0.5f, 0.44721359549995794f, 0.35355339059327376f,
+                               0.33333333333333333f, 0.31622776601683794f, 0.27735009811261456f, 0.23570226039551584f};
+// ... for an offset only known at run time (moments_group8: a lane's window column), as a chain of selects: no load from the table
+__device__ __forceinline__ float inv_len7(int xx, int yy) {
+    float v = kInvLen7[8];
+#pragma unroll
+    for (int i = 7; i >= 0; i--) v = xx * xx + yy * yy == kLen2_7[i] ? kInvLen7[i] : v;
+    return v;
+}
+
+// ---- the estimate, stated once: every moments kernel (svgf_kernels.hip, and moments_lds_kernel below) is built from these ----
+// Reference form: the tap weight through edge_weight (moments_pixel, moments3x3_shfl_kernel, moments_group8<ST, 0>).
+struct MomRefCentre { float lc, zc; float3 nc; float il, phi_d; };
+__device__ __forceinline__ MomRefCentre mom_ref_centre(float4 colour, float4 motion, uint2 normal, float phi_colour) {
+    MomRefCentre c;
+    float dzc;
+    c.lc = lum_exact(colour.x, colour.y, colour.z);
+    depth_of(motion, c.zc, dzc);
+    c.nc = normal_of(normal);
+    c.il = hw_rcp(phi_colour);                                        // :460
+    c.phi_d = fmaxf(dzc, 1e-8f) * 3.0f;                               // :461
+    return c;
+}
+// lum, zp, np: the tap's luminance, depth (depth_of) and normal; (xx, yy): its offset from the centre
+__device__ __forceinline__ float mom_ref_weight(const MomRefCentre& c, float lum, float zp, float3 np, int xx, int yy, float phi_normal) {
+    const float len = sqrtf((float)(xx * xx + yy * yy));              // :488 (IEEE sqrt of a small integer: the value a constant would have)
+    const float iz = (xx == 0 && yy == 0) ? 0.0f : hw_rcp(c.phi_d * len);   // phiDepth == 0 -> wZ = 0, :420
+    return edge_weight(fabsf(c.lc - lum), c.il, fabsf(c.zc - zp), iz, dot3_fma(c.nc, np), phi_normal);
+}
+
+// Fused-exponent form: the weight is ONE exp2 of the value below (moments_taps49, moments_group8<ST, 1>).  il and the depth scales carry log2(e).
+struct MomCentre { float lc, zc, ncz; uint32_t nc01; float il; };
+// log2(e) / phiDepth at distance 1 (:461); dz_raw: the centre's ddepth as stored
+__device__ __forceinline__ float mom_depth_scale(float zc, float dz_raw) { return hw_rcp(fmaxf(zc == kSkyZ ? 0.0f : dz_raw, 1e-8f) * 3.0f) * kLog2e; }
+// lum, z, (n01, nz): the tap's luminance, depth (0 -> 1e30) and normal {(nx,ny) half bits, nz}; izk: the depth scale at the tap's distance (not read
+// for the centre tap: phiDepth == 0 -> wZ = 0, :420); e0: the uniform form's exponent of the normal term.
+//   kTapsUniform  the normal term is e0;   kTapsGeneral  n.n' per tap;
+//   kTapsNaN      the luminance and depth terms as the reference has them: `max(term, 0.0)` is CUDA's fmax, which drops a NaN (:424)
+template <int MODE>
+__device__ __forceinline__ float mom_tap_exponent(const MomCentre& c, float lum, float z, uint32_t n01, float nz, bool centre_tap, float izk, float phi_n, float e0) {
+    float e = e0;
+    if constexpr (MODE != kTapsUniform) e = hw_log2(clamp01(fmaf(nz, c.ncz, dot2_h2(n01, c.nc01)))) * phi_n;
+    if constexpr (MODE == kTapsNaN) e -= fmaxf(fabsf(lum - c.lc) * c.il, 0.0f);
+    else e = fmaf(-fabsf(lum - c.lc), c.il, e);
+    if (!centre_tap) {
+        if constexpr (MODE == kTapsNaN) e -= fmaxf(fabsf(z - c.zc) * izk, 0.0f);         // (a NaN depth)
+        else e = fmaf(-fabsf(z - c.zc), izk, e);
+    }
+    return e;
+}
+
+// :505-516: the weighted sums to {colour, variance of the luminance}; h: the pixel's history length (< 4).  Stored unclamped.
+__device__ __forceinline__ float4 moments_resolve(float sw, float sr, float sg, float sb, float sm1, float sm2, float h) {
+    sw = fmaxf(sw, 1e-6f);                                            // :505
+    const float inv = 1.0f / sw;
+    sm1 *= inv; sm2 *= inv;
+    return make_float4(sr * inv, sg * inv, sb * inv, (sm2 - sm1 * sm1) * (4.0f / h));   // :507-516
+}
+
 struct MomSums { float sw, sm2; f32x2 srg, sbm; };
 
-// e0: the uniform form's exponent of the normal term (wave-uniform)
+// iz: the centre's depth scale by len_class7
 template <int MODE>
 __device__ __forceinline__ void moments_taps49(const f32x4* recA, const f32x2* recL, const f32x2* recN, const float* recC,
-                                               const int (&rowbase)[2 * kMR + 1], const MomCentre& c, float phi_n, float e0, MomSums& s) {
+                                               const int (&rowbase)[2 * kMR + 1], const MomCentre& c, const float (&iz)[9], float phi_n, float e0, MomSums& s) {
     constexpr int NW = 2 * kMR + 1, NT = NW * NW, D = kMTapDepth;
     f32x4 qA[NT];
     f32x2 qL[NT], qN[NT];
@@ -67,21 +129,8 @@ __device__ __forceinline__ void moments_taps49(const f32x4* recA, const f32x2* r
         const int yy = t / NW - kMR, xx = t % NW - kMR;
         const f32x4 A = qA[t];
         const f32x2 L = qL[t];
-        float e;
-        if constexpr (MODE == kTapsUniform) {
-            e = e0;
-        } else {
-            const f32x2 N = qN[t];
-            const float d = clamp01(fmaf(N.y, c.ncz, dot2_h2(__float_as_uint(N.x), c.nc01)));
-            e = hw_log2(d) * phi_n;
-        }
-        if constexpr (MODE == kTapsNaN) e -= fmaxf(fabsf(L.x - c.lc) * c.il, 0.0f);      // fmax(NaN, 0) = 0, :424
-        else e = fmaf(-fabsf(L.x - c.lc), c.il, e);
-        if (xx != 0 || yy != 0) {                                                        // phiDepth == 0 -> wZ = 0 at the centre, :420
-            if constexpr (MODE == kTapsNaN) e -= fmaxf(fabsf(L.y - c.zc) * c.iz[len_class7(xx, yy)], 0.0f);   // fmax(NaN, 0) = 0, :424 (a NaN depth)
-            else e = fmaf(-fabsf(L.y - c.zc), c.iz[len_class7(xx, yy)], e);
-        }
-        const float w = hw_exp2(e);
+        const f32x2 N = MODE == kTapsUniform ? (f32x2){0.f, 0.f} : qN[t];               // (the uniform form reads no normal record)
+        const float w = hw_exp2(mom_tap_exponent<MODE>(c, L.x, L.y, __float_as_uint(N.x), N.y, xx == 0 && yy == 0, iz[len_class7(xx, yy)], phi_n, e0));
         s.sw += w;                                                                       // :497-499
         s.srg = __builtin_elementwise_fma((f32x2){w, w}, (f32x2){A.x, A.y}, s.srg);
         s.sbm = __builtin_elementwise_fma((f32x2){w, w}, (f32x2){A.z, A.w}, s.sbm);
@@ -213,13 +262,13 @@ __global__ __launch_bounds__(kMTX* kRS, 4) void moments_lds_kernel(Geo g, Moment
         for (int r = 0; r <= 2 * kMR; r++) { int sl = slot0 + rg + r; sl = sl >= kMRing ? sl - kMRing : sl; rowbase[r] = sl * WL + col; }
         const int ci = rowbase[kMR] + kMR;
         const f32x2 cL = recL[ci], cN = recN[ci];
-        MomCentre c;
-        c.lc = cL.x; c.zc = cL.y; c.ncz = cN.y; c.nc01 = __float_as_uint(cN.x); c.il = il;
+        const MomCentre c{cL.x, cL.y, cN.y, __float_as_uint(cN.x), il};
         const float h = (float)cen.h;                                               // :442
-        const float dzc = c.zc == kSkyZ ? 0.0f : __uint_as_float(cen.dz);
-        const float izb = hw_rcp(fmaxf(dzc, 1e-8f) * 3.0f) * kLog2e;                // :461
-        c.iz[0] = izb; c.iz[1] = izb * 0.70710678118654752f; c.iz[2] = izb * 0.5f; c.iz[3] = izb * 0.44721359549995794f; c.iz[4] = izb * 0.35355339059327376f;
-        c.iz[5] = izb * 0.33333333333333333f; c.iz[6] = izb * 0.31622776601683794f; c.iz[7] = izb * 0.27735009811261456f; c.iz[8] = izb * 0.23570226039551584f;
+        const float izb = mom_depth_scale(c.zc, __uint_as_float(cen.dz));
+        float iz[9];
+        iz[0] = izb;
+#pragma unroll
+        for (int k = 1; k < 9; k++) iz[k] = izb * kInvLen7[k];
         // every wave's word of every ring row (lanes 0 .. kBadWord-1) and the workgroup's sticky word (lane kBadWord): one read, one compare
         const unsigned long long flagged = __builtin_amdgcn_ballot_w64(lane <= kBadWord && mflag[lane <= kBadWord ? lane : 0] != 0u);
         const bool uniform = !a.no_fastpath && (flagged & ((1ull << kBadWord) - 1ull)) == 0ull;
@@ -227,31 +276,27 @@ __global__ __launch_bounds__(kMTX* kRS, 4) void moments_lds_kernel(Geo g, Moment
         // centre itself among them — which `max(., 0.0)` = fmax turns into "no term" (:424): every pixel's fused-exponent sums are NaN then
         const bool exact = (flagged >> kBadWord) != 0ull || !(il < __builtin_inff());
         MomSums s{0.0f, 0.0f, {0.f, 0.f}, {0.f, 0.f}};
-        // a cleared sky texel (zero normal): every weight is exactly 0, the result (0,0,0,0) while the window is finite (see moments_pixel)
+        // a cleared sky texel (zero normal): every weight is exactly 0, the result (0,0,0,0) while the window is finite (see moments_pixel).
+        // (is_zero_normal on the record's layout: nz is staged as a float)
         const bool zero_normal = !exact && ((c.nc01 & 0x7fff7fffu) == 0u) && (c.ncz == 0.0f);
         const bool need = (h < 4.0f) && !zero_normal && (j + rg < j1);
         if (wave_any(need)) {
-            if (uniform) moments_taps49<kTapsUniform>(recA, recL, recN, recC, rowbase, c, phi_n, e0, s);
-            else moments_taps49<kTapsGeneral>(recA, recL, recN, recC, rowbase, c, phi_n, e0, s);
+            if (uniform) moments_taps49<kTapsUniform>(recA, recL, recN, recC, rowbase, c, iz, phi_n, e0, s);
+            else moments_taps49<kTapsGeneral>(recA, recL, recN, recC, rowbase, c, iz, phi_n, e0, s);
             if (exact) {
                 // A workgroup that has staged a non-finite texel: the pixels whose sums came out NaN — every pixel with a NaN (or inf - inf, 0 x inf)
                 // in its window, and no other — are evaluated again the reference's way; the others keep the bits every other workgroup would
                 // give them, however the frame is cut into tiles, bands or strips (round 4 took the exact form for the whole workgroup).
-                const bool redo = need && (__builtin_isunordered(s.sw, s.sm2) | __builtin_isunordered(s.srg.x, s.srg.y) | __builtin_isunordered(s.sbm.x, s.sbm.y));
+                const bool redo = need && sums_hold_nan(s.sw, s.srg.x, s.srg.y, s.sbm.x, s.sbm.y, s.sm2);
                 if (wave_any(redo)) {
                     MomSums s2{0.0f, 0.0f, {0.f, 0.f}, {0.f, 0.f}};
-                    moments_taps49<kTapsNaN>(recA, recL, recN, recC, rowbase, c, phi_n, e0, s2);
+                    moments_taps49<kTapsNaN>(recA, recL, recN, recC, rowbase, c, iz, phi_n, e0, s2);
                     if (redo) s = s2;
                 }
             }
         }
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f * (4.0f / h));
-        if (!zero_normal) {
-            const float sw = fmaxf(s.sw, 1e-6f);                                    // :505
-            const float inv = 1.0f / sw;
-            const float m1 = s.sbm.y * inv, m2 = s.sm2 * inv;
-            o = make_float4(s.srg.x * inv, s.srg.y * inv, s.sbm.x * inv, (m2 - m1 * m1) * (4.0f / h));   // :507-516
-        }
+        if (!zero_normal) o = moments_resolve(s.sw, s.srg.x, s.srg.y, s.sbm.x, s.sbm.y, s.sm2, h);
         if (more) {
             lds_barrier();
             commit(slot0, fs);
