@@ -152,6 +152,14 @@ def taa(W, H, storage, filtered, history, out, *, geo=None, nthreads=1):
     assert rc == 0
 
 
+def srgb(a):
+    """ToSRGB (src/Filter.cuh:145-148) of every element of a float32 array."""
+    a = np.ascontiguousarray(a, np.float32)
+    out = np.empty_like(a)
+    lib().svgf_oracle_srgb(_p(a), _p(out), C.c_size_t(a.size))
+    return out
+
+
 def albedo(mode, W, rows, storage, inp, alb, out):
     """Albedo demodulation (mode 0) / re-modulation (mode 1): the build's own definition (the reference has none)."""
     rc = lib().svgf_oracle_albedo(int(mode), W, rows, STORAGE[storage], _p(inp), _p(alb), _p(out))
@@ -219,3 +227,106 @@ class Pipeline:
         self.taps["feedback"] = self.colour[P].copy()
         self.P ^= 1
         return self.filt[pp]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The reference's own filter source, host-compiled (oracle/ref_harness.cpp, `make _ref`): what the oracle is pinned against.
+# fp16 storage only — the reference's kernels take half4* / half2*; the fp32 oracle path stays pinned by oracle/svgf_numpy.py alone.
+
+REFERENCE_DIR = os.environ.get("SVGF_REFERENCE_DIR", "/root/reference")
+_REF_DIR = os.path.join(_HERE, "_ref")
+_REF_LIBS = {False: os.path.join(_REF_DIR, "libsvgf_ref.so"), True: os.path.join(_REF_DIR, "libsvgf_ref_fma.so")}
+UV_FETCH_RAW_BITS, UV_FETCH_AS_HALF = 0, 1      # what tex2D<float4> returns from the 8-byte UV texel: = mesh_id_test 0 / 1 of the oracle
+_ref_libs = {}
+
+
+def reference_available() -> bool:
+    """The reference checkout is present, so oracle/_ref can (and must) be built."""
+    return os.path.isfile(os.path.join(REFERENCE_DIR, "src", "Filter.cuh"))
+
+
+def build_ref(force: bool = False):
+    """Copies the reference's Filter.cuh to oracle/_ref/src/ and compiles it with ref_harness.cpp and the stand-in headers of ref_shim/ into
+    oracle/_ref/libsvgf_ref.so, then — as far as this host can (-mfma), like the oracle's own envelope flavours — its -ffp-contract=fast twin.
+    -> the path of the former, or None (one line printed) without a reference."""
+    if not reference_available():
+        print(f"oracle: no reference checkout at {REFERENCE_DIR}: oracle/_ref not built, the recorded fixtures under tests/golden/ stand in")
+        return None
+    make = ["make", "-C", _HERE] + (["-B"] if force else []) + [f"SVGF_REFERENCE_DIR={REFERENCE_DIR}"]
+    subprocess.check_call(make + ["_ref"], stdout=subprocess.DEVNULL)
+    try:
+        subprocess.check_call(make + ["_ref_fma"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    except subprocess.CalledProcessError:
+        pass                                   # (ref_lib(fma=True) raises EnvelopeUnavailable, the twin tests skip)
+    return _REF_LIBS[False]
+
+
+_VP, _FP = C.c_void_p, C.c_float
+_REF_ARGTYPES = {
+    "svgf_ref_set_uv_fetch": [C.c_int],
+    "svgf_ref_temporal": [C.c_int, C.c_int] + [_VP] * 11 + [_FP, _FP, C.c_int],
+    "svgf_ref_moments": [C.c_int, C.c_int] + [_VP] * 6 + [_FP, _FP],
+    "svgf_ref_atrous": [C.c_int, C.c_int] + [_VP] * 6 + [C.c_int, _FP, _FP, C.c_int],
+    "svgf_ref_taa": [C.c_int, C.c_int, _VP, _VP],
+    "svgf_ref_tonemap": [C.c_int, C.c_int, _VP, _VP],
+    "svgf_ref_guard_selftest": [C.c_int] * 6 + [_VP],
+}
+
+
+def ref_lib(fma: bool = False):
+    """The built reference library (never built implicitly: __graft_entry__.build() or `make -C oracle _ref` does that)."""
+    if fma not in _ref_libs:
+        if not os.path.exists(_REF_LIBS[fma]):
+            if fma and os.path.exists(_REF_LIBS[False]):
+                raise EnvelopeUnavailable(f"{_REF_LIBS[True]} is not built (x86 with FMA only)")
+            raise FileNotFoundError(f"{_REF_LIBS[fma]} is not built: run __graft_entry__.build() or `make -C oracle _ref`")
+        L = C.CDLL(_REF_LIBS[fma])
+        for name, args in _REF_ARGTYPES.items():
+            getattr(L, name).argtypes, getattr(L, name).restype = args, C.c_int
+        _ref_libs[fma] = L
+    return _ref_libs[fma]
+
+
+def ref_guard_selftest(W, H, x, y, dx, dy):
+    """The runner's check that a thread stores at its own pixel only, on a kernel of the harness's own: the thread of pixel (x, y) also stores at
+    (x + dx, y + dy).  -> (return value of the launch: 0, or -2 for a stray store; the plane after the launch)."""
+    plane = np.zeros((H, W), np.uint8)
+    rc = ref_lib().svgf_ref_guard_selftest(W, H, x, y, dx, dy, _p(plane))
+    return rc, plane
+
+
+def _ref_rc(rc, what):
+    assert rc != -2, f"reference {what}: a thread stored outside its own pixel"
+    assert rc == 0, f"reference {what}: rc {rc}"
+
+
+def ref_temporal(W, H, prev_colour, colour, gb_cur, gb_prev, hist, mom_cur, mom_prev, *, depth_threshold, normal_threshold, history_base,
+                 uv_fetch=UV_FETCH_AS_HALF, fma=False):
+    """TemporalFilter in place, as the reference runs it: `colour` holds the radiance going in and the result coming out, `hist` the single
+    history plane (read at the reprojected pixel as it was before the launch, written at the own pixel), `mom_cur` is written."""
+    L = ref_lib(fma)
+    rc = L.svgf_ref_set_uv_fetch(int(uv_fetch))
+    assert rc == 0, f"reference: unknown UV fetch mode {uv_fetch}"
+    _ref_rc(L.svgf_ref_temporal(W, H, _p(prev_colour), _p(colour), _p(gb_cur["motion"]), _p(gb_cur["normal"]), _p(gb_cur["uv"]),
+                                _p(gb_prev["motion"]), _p(gb_prev["normal"]), _p(gb_prev["uv"]), _p(hist), _p(mom_cur), _p(mom_prev),
+                                C.c_float(depth_threshold), C.c_float(normal_threshold), int(history_base)), "TemporalFilter")
+
+
+def ref_moments(W, H, colour, out, mom, gb, hist, *, phi_colour, phi_normal, fma=False):
+    _ref_rc(ref_lib(fma).svgf_ref_moments(W, H, _p(colour), _p(out), _p(mom), _p(gb["motion"]), _p(gb["normal"]), _p(hist),
+                                          C.c_float(phi_colour), C.c_float(phi_normal)), "FilterMoments")
+
+
+def ref_atrous(W, H, src, dst, render_output, gb, hist, *, step, phi_colour, phi_normal, iteration, fma=False):
+    _ref_rc(ref_lib(fma).svgf_ref_atrous(W, H, _p(src), _p(gb["motion"]), _p(gb["normal"]), _p(hist), _p(dst), _p(render_output), int(step),
+                                         C.c_float(phi_colour), C.c_float(phi_normal), int(iteration)), "FilterKernel")
+
+
+def ref_taa(W, H, filtered, out, *, fma=False):
+    """TAAFilterKernel in place: `out` holds the previous output going in (the history) and the new one coming out."""
+    _ref_rc(ref_lib(fma).svgf_ref_taa(W, H, _p(filtered), _p(out)), "TAAFilterKernel")
+
+
+def ref_tonemap(W, H, inp, out, *, fma=False):
+    """TonemapKernel on float32 (H, W, 4) planes."""
+    _ref_rc(ref_lib(fma).svgf_ref_tonemap(W, H, _p(inp), _p(out)), "TonemapKernel")

@@ -4,11 +4,11 @@
 // link, import or execute this file.  Only tests/, __graft_entry__.smoke() and the
 // cpu_baseline leg of bench.py use it, and only as the checker / reported baseline.
 //
-// PARITY UNPINNED: the reference repository has no tests, golden vectors or CPU
-// implementation of the filter and its CUDA sources cannot be
-// built in this image (no nvcc, glm submodule empty).  This restatement is pinned
-// instead by (a) hand-derivable known-answer cases and (b) an independently written
-// NumPy restatement (oracle/svgf_numpy.py); see tests/test_oracle_*.py.
+// PARITY: the reference repository has no tests, golden vectors or CPU implementation of the filter, and its
+// application cannot be built without its toolchain.  Its filter source can: ref_harness.cpp compiles it for the host against the
+// stand-in headers of ref_shim/, and the fp16 path of this restatement is held to that build bit for bit
+// (tests/test_reference_parity.py).  The fp32 storage path and the G-buffer adapter are pinned by (a) hand-derivable known-answer
+// cases and (b) an independently written NumPy restatement (oracle/svgf_numpy.py); see tests/test_oracle_*.py.
 //
 // Each function cites the reference lines (under /root/reference/) it follows.
 // Arithmetic is fp32 with the reference's fp64 islands kept;
@@ -555,6 +555,10 @@ int svgf_oracle_pack_gbuffer(int W, int H, const float* position, const float* n
 
 // envelope build "hwulp" only (a no-op in every other build): which of its possible "transcendental units" the build models
 void svgf_oracle_set_hw_ulp_seed(uint32_t seed) { g_hw_ulp_seed = seed; }
+
+// ToSRGB (Filter.cuh:145-148) on n floats: what TonemapKernel (:159-175) stores and what TAAFilterKernel ends with (:353), exported so that
+// it can be held to the reference build on its own (tests/test_reference_parity.py)
+void svgf_oracle_srgb(const float* in, float* out, size_t n) { for (size_t i = 0; i < n; i++) out[i] = to_srgb(in[i]); }
 
 // converters exported so the tests can pin them against numpy's float16
 uint16_t svgf_oracle_f2h(float f) { return f2h(f); }

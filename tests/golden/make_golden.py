@@ -1,7 +1,10 @@
-"""Generates the committed golden fixtures from the CPU oracle (run from the repo root:
+"""Generates the committed golden fixtures (run from the repo root:
     python tests/golden/make_golden.py).
-The reference holds no vectors for this path, so these pin the ORACLE's behaviour (and the synthetic
-generator) against silent drift; GPU tests compare the HIP path with them as well."""
+The reference holds no vectors for this path.  atrous_*, pipeline_* and config1_* are made from the CPU oracle: they pin the
+ORACLE's behaviour (and the synthetic generator) against silent drift.  ref_stages_* and ref_sequence_* are made from the host build of the
+reference's own filter source (oracle/_ref, __graft_entry__.build()): they record what the REFERENCE computes, so that the oracle (CPU) and the
+HIP kernels (GPU) can be held to it where the reference checkout is absent.  They hold outputs and the parameters that regenerate the inputs
+(tests/reference_cases.py) — data only."""
 import os
 import sys
 
@@ -67,10 +70,29 @@ def config1(W=256, H=256):
     np.savez_compressed(os.path.join(HERE, "config1_256x256.npz"), input_sums=sums, **out)
 
 
+def reference_fixtures():
+    """-> {file name: dict of arrays}: the reference build's outputs for tests/reference_cases.py's fixture cases, with their parameters"""
+    from tests import reference_cases as rc
+    W, H = rc.FIXTURE_SIZE
+    side = rc.ReferenceSide(orc)
+    params = {f"param_{k}": np.asarray(v) for k, v in rc.FIXTURE_PARAMS.items()}
+    return {"ref_stages_64x48.npz": dict(params, **rc.fixture_stage_outputs(side)),
+            "ref_sequence_64x48.npz": dict(params, **rc.fixture_sequence_outputs(rc.reference_sequence(orc, W, H)))}
+
+
+def reference():
+    """(needs oracle/_ref: skipped with a line where the reference checkout is absent — the committed files stay as they are)"""
+    if orc.build_ref() is None:
+        return
+    for name, arrays in reference_fixtures().items():
+        np.savez_compressed(os.path.join(HERE, name), **arrays)
+
+
 if __name__ == "__main__":
     atrous_single()
     pipeline()
     config1()
+    reference()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
